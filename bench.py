@@ -7,9 +7,11 @@ forward + Stokes PDE-residual loss + backward + gradient all-reduce + Adam) on s
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (contract in the task statement): metric/value/unit, ms_per_step,
-`roofline` for the dominant kernel (algorithmic bytes / live HIP-event duration) and `cpu_baseline`
-(the CPU oracle timed on this box's host cores, N=1 only).
+Prints ONE JSON line on rank 0: metric/value/unit, ms_per_step, dtype and the configuration.  A plain run
+sets up, warms up, times the K steps and prints that line, nothing else.  `--full` adds what takes runs of its
+own: `roofline` for the dominant kernel (algorithmic bytes / live HIP-event duration, an instrumented pass after
+the timed steps), `hbm_roofline_frac_step` and `cpu_baseline` (the CPU oracle timed on the host cores, N=1 only).
+`--dump-outputs DIR` writes what the last timed step computed (losses, updated weights, weight gradients) as .npy.
 """
 import argparse
 import json
@@ -40,7 +42,12 @@ def parse():
                    help="bf16 with a momentum term runs as 'mixed' (f16 forward tensors, bf16 gradient tensors, see engine.py)")
     p.add_argument("--lambda-mom", type=float, default=1e-6, help="weight of the Stokes momentum residual (CFG-3)")
     p.add_argument("--no-graph", action="store_true", help="eager launches instead of HIP-graph replay")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="also measure the roofline of the dominant kernel (instrumented pass), hbm_roofline_frac_step and "
+                        "the CPU-oracle baseline")
+    p.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                   help="write what the last timed step computed to DIR/<name>.npy (rank 0)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="(with --full) skip the CPU-oracle baseline")
     p.add_argument("--cpu-batch", type=int, default=2)
     p.add_argument("--cpu-steps", type=int, default=3)
     p.add_argument("--backend", type=str, default="nccl", help="torch.distributed backend (nccl = RCCL; gloo for rehearsals)")
@@ -120,6 +127,27 @@ def cpu_baseline(args, H, W):
                        f"1 warm-up step")
 
 
+DUMP_BYTES = 64 << 20         # cap on everything --dump-outputs writes
+
+
+def dump_outputs(outdir, out8, tr):
+    """What the last timed step computed, as a caller of Trainer.train_step sees it: the 8 loss scalars it returns, the
+    flat weight vector after its Adam update and the flat weight gradient it reduced.  An array over its share of
+    DUMP_BYTES is replaced by a fixed, seeded sample of its entries (same indices on every run)."""
+    import numpy as np
+    arrays = {"losses": out8.detach().double().cpu().numpy(),
+              "params": tr.flat.param.detach().float().cpu().numpy(),
+              "grads": tr.flat.grad.detach().float().cpu().numpy()}
+    share = DUMP_BYTES // len(arrays)
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in arrays.items():
+        a = a.reshape(-1)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a[idx]
+        np.save(os.path.join(outdir, name + ".npy"), a)
+
+
 def main():
     args = parse()
     rank = int(os.environ.get("RANK", "0"))
@@ -197,19 +225,23 @@ def main():
     loss = float(out8[0].item())
     if not (loss == loss) or abs(loss) > 1e6:
         raise SystemExit(f"non-finite / diverged loss {loss}")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out8, tr)
 
-    # ---- roofline of the dominant kernel: an instrumented pass of the same steps, HIP events around every
-    #      launch of the conv forward/input-gradient kernel family on the launch stream
     eng = model.engine()
-    nprobe = min(steps, 3)
-    probe = eng.enable_probe(nprobe)
-    for _ in range(nprobe):
-        tr._fwd_bwd(gVTp, uvp, yc, paras, scaler, train=True)
-    torch.cuda.synchronize(dev)
-    roof = eng.probe_summary(probe, HBM_PEAK_GBS)
-    eng.disable_probe()
-    roof["traffic"], roof["traffic_measured_at_commit"] = pmc_traffic(roof["kernel"], B, H, W, args.precision) if roof["kernel"] \
-        else (None, None)
+    roof = None
+    if args.full:
+        # ---- roofline of the dominant kernel: an instrumented pass of the same steps, HIP events around every
+        #      launch of the conv forward/input-gradient kernel family on the launch stream
+        nprobe = min(steps, 3)
+        probe = eng.enable_probe(nprobe)
+        for _ in range(nprobe):
+            tr._fwd_bwd(gVTp, uvp, yc, paras, scaler, train=True)
+        torch.cuda.synchronize(dev)
+        roof = eng.probe_summary(probe, HBM_PEAK_GBS)
+        eng.disable_probe()
+        roof["traffic"], roof["traffic_measured_at_commit"] = pmc_traffic(roof["kernel"], B, H, W, args.precision) \
+            if roof["kernel"] else (None, None)
 
     line = None
     if rank == 0:
@@ -233,11 +265,12 @@ def main():
                                               "gradient tensor, f32 accumulate: the Trainer's choice for bf16 with a momentum term"}[model.precision],
                        "global_batch": world * B, "grid": [H, W], "parallelism": f"dp{world}",
                        "loss": float(loss)},
-            "roofline": roof,
-            "hbm_roofline_frac_step": sps / world * eng.algorithmic_bytes_per_sample(args.precision) / (HBM_PEAK_GBS * 1e9),
         }
-        if world == 1 and not args.no_cpu_baseline:
-            line["cpu_baseline"] = cpu_baseline(args, H, W)
+        if args.full:
+            line["roofline"] = roof
+            line["hbm_roofline_frac_step"] = sps / world * eng.algorithmic_bytes_per_sample(args.precision) / (HBM_PEAK_GBS * 1e9)
+            if world == 1 and not args.no_cpu_baseline:
+                line["cpu_baseline"] = cpu_baseline(args, H, W)
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.barrier()

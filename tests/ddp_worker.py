@@ -87,7 +87,7 @@ def run_bench(rank, world, port, outdir):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     sys.path.insert(0, root)
     sys.argv = ["bench.py", "--gpus", str(world), "--backend", "gloo", "--steps", "3", "--warmup", "2", "--batch", "2",
-                "--size", "64", "150", "--no-cpu-baseline"]
+                "--size", "64", "150", "--full", "--no-cpu-baseline"]
     import bench
     buf = io.StringIO()
     with contextlib.redirect_stdout(buf):
