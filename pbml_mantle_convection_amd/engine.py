@@ -302,16 +302,59 @@ def single_layer_graph(c_in, c_out, k, pad, pad_mode, sym_h, post, act, groups, 
     return NetGraph(c_in, c_out, ch, [node], pad_mode=pad_mode, act=act)
 
 
-def iter_conv_descs(g: NetGraph, N: int, H: int, W: int, precision: str):
-    """(name, forward descriptor, input-gradient descriptor or None) of every convolution launch of the graph at input size
-    N x H x W -- the same shape walk and descriptors as Engine.configure, without touching a device (host-side checks:
-    tests/test_abi_and_host.py compares every launch's bank reach with the bank's size)."""
+# learned padding (BoundaryLearnedConvolution2D): parameter order of the nine banks (the reference's sub-modules)
+BANKS = ("conv", "conv_top_left", "conv_top_right", "conv_bottom_left", "conv_bottom_right", "conv_top", "conv_bottom",
+         "conv_left", "conv_right")
+
+
+def learned_regions(h, w, k, bc_x=1, bc_y=1):
+    """Geometry of the nine banks on an h x w input: (fy, fx, ho, wo, {bank: (sy, sx, sh, sw, dy, dx)}) -- the frame widths,
+    the output size and, per bank, the input rectangle it convolves (valid) and where its result lands in the output.  The
+    strips are k + 1 (k = 5) or k wide, bc > 1 widens them by bc - 1.  Banks come in launch order: the main bank first."""
+    pad_x = k + 1 + (bc_x - 1) if k == 5 else k + (bc_x - 1)
+    pad_y = k + 1 + (bc_y - 1) if k == 5 else k + (bc_y - 1)
+    fx, fy, mh, mw = pad_x - k + 1, pad_y - k + 1, h - k + 1, w - k + 1
+    return fy, fx, mh + 2 * fy, mw + 2 * fx, {
+        "conv": (0, 0, h, w, fy, fx),
+        "conv_left": (0, 0, h, pad_x, fy, 0), "conv_right": (0, w - pad_x, h, pad_x, fy, fx + mw),
+        "conv_bottom": (h - pad_y, 0, pad_y, w, 0, fx), "conv_top": (0, 0, pad_y, w, fy + mh, fx),
+        "conv_bottom_left": (h - pad_y, 0, pad_y, pad_x, 0, 0),
+        "conv_bottom_right": (h - pad_y, w - pad_x, pad_y, pad_x, 0, fx + mw),
+        "conv_top_left": (0, 0, pad_y, pad_x, fy + mh, 0), "conv_top_right": (0, w - pad_x, pad_y, pad_x, fy + mh, fx + mw)}
+
+
+@dataclass
+class ConvShape:
+    """Descriptors of one conv node at a given input size."""
+    dgrad: bool                          # some source needs a gradient
+    d: Optional[L.ConvDesc] = None       # forward
+    dd: Optional[L.ConvDesc] = None      # input gradient (None when no source needs one)
+    final_f32: bool = False              # the head writes its output in f32
+    banks: Optional[dict] = None         # learned padding: bank -> (region, d, dd) in launch order; d / dd stay None
+
+
+def _conv_descs(N, h, w, cs, c_out, k, pad, mode, mc, mcg, sym=(0, 0, 0), out_f32=False, dgrad=True):
+    """Forward descriptor of a conv over one or two concatenated sources of cs channels, and its input gradient: the same
+    kernel on the padded domain (zero pad k - 1, rotated / transposed bank), its output split at cs[0] for two sources."""
+    two = len(cs) > 1
+    d = L.ConvDesc(N, h, w, cs[0], cs[1] if two else 0, c_out, k, pad, mode, mc, sym[0], 0, int(out_f32), sym[1], sym[2])
+    if not dgrad:
+        return d, None
+    ho, wo = h + 2 * pad - k + 1, w + 2 * pad - k + 1
+    return d, L.ConvDesc(N, ho, wo, c_out, 0, sum(cs), k, k - 1, 0, mcg, 0, cs[0] if two else 0, 0)
+
+
+def shape_walk(g: NetGraph, N: int, H: int, W: int, precision: str):
+    """The graph's geometry at input size N x H x W, without touching a device: (size, grad, convs) = every tensor's (H, W),
+    whether it needs a gradient, and a ConvShape per conv node (by index in g.nodes).  Engine.configure plans its buffers and
+    launches on it."""
     mc, _ = DTYPES[precision]
     mcg = L.MC_BF16 if mc == L.MC_MIX16 else mc
     mode = L.PAD_MODES[g.pad_mode]
     size = {0: (H, W + 2 * g.in_pad_w)}
     grad = {0: False}
-    for node in g.nodes:
+    convs: Dict[int, ConvShape] = {}
+    for i, node in enumerate(g.nodes):
         if node.kind == "up":
             size[node.out] = size[node.like] if node.like >= 0 else tuple(v * node.scale for v in size[node.src])
             grad[node.out] = True
@@ -320,46 +363,53 @@ def iter_conv_descs(g: NetGraph, N: int, H: int, W: int, precision: str):
             size[node.out] = tuple(v // node.f for v in size[node.src])
             grad[node.out] = grad[node.src]
             continue
+        h, w = size[node.srcs[0]]
         if node.kind == "cat":
-            size[node.out] = size[node.srcs[0]]
+            if any(size[t] != (h, w) for t in node.srcs) or any(g.channels[t] % 8 for t in node.srcs[:-1]):
+                raise ValueError("torch.cat operands must share H x W and all but the last need C % 8 == 0")
+            size[node.out] = (h, w)
             grad[node.out] = True
             continue
-        h, w = size[node.srcs[0]]
-        cs = [g.channels[i] for i in node.srcs]
+        assert all(size[t] == (h, w) for t in node.srcs), "concat sources must agree in size"
+        cs = [g.channels[t] for t in node.srcs]
+        dgrad = any(grad[t] for t in node.srcs)
         k = node.k
         if node.learned:
-            pad_x = k + 1 + (node.bc_x - 1) if k == 5 else k + (node.bc_x - 1)
-            pad_y = k + 1 + (node.bc_y - 1) if k == 5 else k + (node.bc_y - 1)
-            fx, fy, mh, mw = pad_x - k + 1, pad_y - k + 1, h - k + 1, w - k + 1
-            ho, wo = mh + 2 * fy, mw + 2 * fx
-            for name, (sh, sw) in dict(conv=(h, w), conv_left=(h, pad_x), conv_right=(h, pad_x), conv_bottom=(pad_y, w),
-                                       conv_top=(pad_y, w), conv_bottom_left=(pad_y, pad_x), conv_bottom_right=(pad_y, pad_x),
-                                       conv_top_left=(pad_y, pad_x), conv_top_right=(pad_y, pad_x)).items():
-                d = L.ConvDesc(N, sh, sw, cs[0], 0, node.c_out, k, 0, L.PAD_MODES["zeros"], mc, node.sym_h, 0, 0)
-                dd = L.ConvDesc(N, sh - k + 1, sw - k + 1, node.c_out, 0, cs[0], k, k - 1, 0, mcg, 0, 0, 0)
-                yield node.name + name, d, dd
+            assert len(cs) == 1, "learned padding takes one source tensor"
+            _, _, ho, wo, regs = learned_regions(h, w, k, node.bc_x, node.bc_y)
+            if any(sy < 0 or sx < 0 or sh < k or sw < k for sy, sx, sh, sw, _, _ in regs.values()):
+                raise ValueError(f"{node.name}: input {h}x{w} too small for learned padding")
+            convs[i] = ConvShape(dgrad, banks={
+                name: (r, *_conv_descs(N, r[2], r[3], cs, node.c_out, k, 0, L.PAD_MODES["zeros"], mc, mcg, (node.sym_h, 0, 0)))
+                for name, r in regs.items()})
         else:
             ho, wo = h + 2 * node.pad - k + 1, w + 2 * node.pad - k + 1
             final_f32 = node.post == L.POST_NONE and node is g.nodes[-1] and mc != L.MC_F32 and node.c_out <= 16
-            d = L.ConvDesc(N, h, w, cs[0], cs[1] if len(cs) > 1 else 0, node.c_out, k, node.pad, mode, mc, node.sym_h, 0,
-                           int(final_f32), node.sym_v, node.sym_hv)
-            dd = None
-            if any(grad[i] for i in node.srcs):
-                dd = L.ConvDesc(N, ho, wo, node.c_out, 0, sum(cs), k, k - 1, 0, mcg, 0, cs[0] if len(cs) > 1 else 0, 0)
-            yield node.name, d, dd
+            convs[i] = ConvShape(dgrad, *_conv_descs(N, h, w, cs, node.c_out, k, node.pad, mode, mc, mcg,
+                                                     (node.sym_h, node.sym_v, node.sym_hv), final_f32, dgrad), final_f32)
         size[node.out] = (ho, wo)
         grad[node.out] = True
         if node.pool > 1:
             size[node.pooled] = (ho // node.pool, wo // node.pool)
             grad[node.pooled] = True
+    return size, grad, convs
+
+
+def iter_conv_descs(g: NetGraph, N: int, H: int, W: int, precision: str):
+    """(name, forward descriptor, input-gradient descriptor or None) of every convolution launch of the graph at input size
+    N x H x W, from the shape walk Engine.configure plans on (host-side checks: tests/test_abi_and_host.py compares every
+    launch's bank reach with the bank's size)."""
+    for i, c in shape_walk(g, N, H, W, precision)[2].items():
+        if c.banks is None:
+            yield g.nodes[i].name, c.d, c.dd
+        else:
+            for name, (_, d, dd) in c.banks.items():
+                yield g.nodes[i].name + name, d, dd
 
 
 # ------------------------------------------------------------------------------------------------
 # bicubic tap tables (nn.Upsample(mode='bicubic', align_corners=False), A = -0.75), built in f64
 # ------------------------------------------------------------------------------------------------
-BICUBIC_WALK = os.environ.get("MANTLE_BICUBIC_WALK", "1") != "0"    # row-walk adjoint (mc_bicubic_bwd_walk) vs the tiled kernel
-
-
 def bicubic_tables(n_in: int, n_out: int):
     A = -0.75
     scale = n_in / n_out
@@ -425,15 +475,6 @@ class Engine:
         self.mc_gdtype, self.g_dtype = (L.MC_BF16, torch.bfloat16) if self.mc_dtype == L.MC_MIX16 else (self.mc_dtype, self.t_dtype)
         self.shape = None
         self._tables = {}
-        # filter-gradient kernels on a second stream: 0 = never, 1 = every layer, 2 = only layers of <= 128 x 128 pixels
-        # (their launches are latency-bound and leave most of the chip idle)
-        self.wfin_per_layer = os.environ.get("MANTLE_WFIN_PER_LAYER", "1") != "0"   # A/B on MI355X: -0.14 ms/step (the combine leaves the tail of the step)
-        # A/B on MI355X, round 2 (CFG-3, B = 32): 0 = 12.6 / 11.0 ms (mixed / bf16), 1 = 13.1 / 11.6, 2 = 12.8 / 11.3.  The two
-        # full-chip kernels of a layer only time-slice when they run side by side (each takes twice its stand-alone time),
-        # while every cross-queue dependency of the captured step costs 12-17 us (tools/step_timeline.py): one stream wins.
-        # (Round 1 measured the opposite, -0.25 ms for 1, with the slower filter-gradient kernel of that time.)
-        self.overlap_wgrad = int(os.environ.get("MANTLE_OVERLAP_WGRAD", "0"))
-        self.overlap_pack = int(os.environ.get("MANTLE_OVERLAP_PACK", "0"))    # the three bank-packing launches beside the input pack
         # bit 0: GroupNorm + activation applied by the consumers on load (conv, filter gradient, bicubic) instead of a
         # stand-alone pass that materialises the activated tensor; bit 1: the GroupNorm-backward reduction fused into the
         # epilogue of the input-gradient launch (single-consumer tensors).  0 = the round-1 unfused chain (A/B, tests).
@@ -470,14 +511,14 @@ class Engine:
             raise ValueError(f"input H, W must be divisible by {g.divisor}")
         self.device = device
         self.N = N
-        T: Dict[int, _T] = {tid: _T(C=c) for tid, c in g.channels.items()}
-        T[0].H, T[0].W, T[0].requires_grad = H, W + 2 * g.in_pad_w, False
+        size, grad, convs = shape_walk(g, N, H, W, self.precision)
+        T: Dict[int, _T] = {tid: _T(C=c, H=size[tid][0], W=size[tid][1], requires_grad=grad[tid])
+                            for tid, c in g.channels.items()}
         mode = L.PAD_MODES[g.pad_mode]
         self.mode = mode
         f32 = dict(dtype=torch.float32, device=device)
         self.plan = []
         max_dy = 0
-        max_wg = 0
 
         def cb8(c, h, w):
             return torch.empty((N, (c + 7) // 8, h, w, 8), dtype=self.t_dtype, device=device)
@@ -493,69 +534,46 @@ class Engine:
                 cons[i].append(node)
         self.cons = cons
         self.prod = {}                       # tensor id -> plan entry of the conv that produced it (full-resolution output)
-        H0, W0 = T[0].H, T[0].W
-        for node in g.nodes:
+        for i, node in enumerate(g.nodes):
             if node.kind == "up":
-                s = T[node.src]
-                if node.like >= 0:
-                    ho, wo = T[node.like].H, T[node.like].W
-                else:
-                    ho, wo = s.H * node.scale, s.W * node.scale
-                o = T[node.out]
-                o.H, o.W = ho, wo
-                o.buf = cb8(o.C, ho, wo)
-                tabs = (self._table(s.H, ho), self._table(s.W, wo))
+                s, o = T[node.src], T[node.out]
+                o.buf = cb8(o.C, o.H, o.W)
+                tabs = (self._table(s.H, o.H), self._table(s.W, o.W))
                 e = dict(node=node, tabs=tabs, dsrc=cb8g(s.C, s.H, s.W),
-                         maxtaps=tuple(int(np.diff(bicubic_tables(a, b)[2]).max()) for a, b in ((s.H, ho), (s.W, wo))))
-                if ho > 3 * s.H or wo > 3 * s.W:
+                         maxtaps=tuple(int(np.diff(bicubic_tables(a, b)[2]).max()) for a, b in ((s.H, o.H), (s.W, o.W))))
+                if o.H > 3 * s.H or o.W > 3 * s.W:
                     # scale factor > 3: the adjoint runs as two 1-D passes through an f32 workspace (tap lists too long
                     # for the tiled kernel's window)
-                    e["bws"] = torch.empty((N, (s.C + 7) // 8, s.H, wo, 8), **f32)
+                    e["bws"] = torch.empty((N, (s.C + 7) // 8, s.H, o.W, 8), **f32)
                 self.plan.append(e)
                 continue
             if node.kind == "pool":
-                s, o = T[node.src], T[node.out]
-                o.H, o.W = s.H // node.f, s.W // node.f
+                o = T[node.out]
                 o.buf = cb8(o.C, o.H, o.W)
-                o.requires_grad = s.requires_grad
                 self.plan.append(dict(node=node, dsum=cb8g(o.C, o.H, o.W)))
                 continue
             if node.kind == "cat":
-                srcs = [T[i] for i in node.srcs]
                 o = T[node.out]
-                o.H, o.W = srcs[0].H, srcs[0].W
-                if any((t.H, t.W) != (o.H, o.W) for t in srcs) or any(t.C % 8 for t in srcs[:-1]):
-                    raise ValueError("torch.cat operands must share H x W and all but the last need C % 8 == 0")
                 o.buf = cb8(o.C, o.H, o.W)
                 self.plan.append(dict(node=node))
                 continue
-            srcs = [T[i] for i in node.srcs]
-            h, w = srcs[0].H, srcs[0].W
-            for s in srcs:
-                assert (s.H, s.W) == (h, w), "concat sources must agree in size"
-            if node.learned:
-                self.plan.append(self._plan_learned(node, srcs, T, cb8, cb8g, f32, N, device))
-                e = self.plan[-1]
-                max_dy = max(max_dy, N * e["coutp"] * T[node.out].H * T[node.out].W)
-                continue
-            final_f32 = (node.post == L.POST_NONE and node is g.nodes[-1] and self.mc_dtype != L.MC_F32
-                         and node.c_out <= 16)
-            ho, wo = h + 2 * node.pad - node.k + 1, w + 2 * node.pad - node.k + 1
-            omode = int(final_f32)
-            d = L.ConvDesc(N, h, w, srcs[0].C, srcs[1].C if len(srcs) > 1 else 0, node.c_out, node.k, node.pad,
-                           mode, self.mc_dtype, node.sym_h, 0, omode, node.sym_v, node.sym_hv)
+            srcs = [T[t] for t in node.srcs]
             o = T[node.out]
-            o.H, o.W = ho, wo
+            h, w, ho, wo = srcs[0].H, srcs[0].W, o.H, o.W
+            if node.learned:
+                e = self._plan_learned(node, convs[i], srcs[0], o, cb8, cb8g, f32)
+                if node.pool > 1:
+                    T[node.pooled].buf = cb8(node.c_out, T[node.pooled].H, T[node.pooled].W)
+                self.plan.append(e)
+                max_dy = max(max_dy, N * e["coutp"] * ho * wo)
+                continue
+            d, dd, final_f32 = convs[i].d, convs[i].dd, convs[i].final_f32
             tiles = L.call("mc_conv_tiles", C.byref(d))
             if tiles <= 0:
                 raise L.MantleHipError(f"unsupported convolution configuration for {node.name} "
                                        f"({self.precision}, c_in={srcs[0].C}+{d.c_in1}, c_out={node.c_out}, k={node.k})")
             coutp = ((node.c_out + 7) // 8) * 8
-            cin_tot = sum(s.C for s in srcs)
-            # dgrad = the same kernel on the padded domain: zero pad k-1, rotated/transposed bank
-            dd = L.ConvDesc(N, ho, wo, node.c_out, 0, cin_tot, node.k, node.k - 1, 0, self.mc_gdtype, 0,
-                            srcs[0].C if len(srcs) > 1 else 0, 0)
-            need_dgrad = any(s.requires_grad for s in srcs)
+            need_dgrad = convs[i].dgrad
             e = dict(node=node, desc=d, ddesc=dd, tiles=tiles, coutp=coutp,
                      Y=(torch.empty((N, (node.c_out + 7) // 8, ho, wo, 8), dtype=torch.float32, device=device)
                         if final_f32 else cb8(node.c_out, ho, wo)),
@@ -585,9 +603,7 @@ class Engine:
                 if ho * wo <= self.gn_small_pix and (node.c_out // node.groups) in (1, 2, 4, 8):
                     e["pc"] = torch.empty((N, coutp, 2), **f32)
             if node.pool > 1:
-                p = T[node.pooled]
-                p.H, p.W = ho // node.pool, wo // node.pool
-                p.buf = cb8(node.c_out, p.H, p.W)
+                T[node.pooled].buf = cb8(node.c_out, T[node.pooled].H, T[node.pooled].W)
             if need_dgrad:
                 e["dbank"] = torch.empty(L.call("mc_packed_weight_bytes", C.byref(d), 1), dtype=torch.uint8,
                                          device=device)
@@ -618,23 +634,10 @@ class Engine:
             e["wpart"] = torch.empty(L.call("mc_wgrad_partial_bytes", C.byref(d)), dtype=torch.uint8, device=device)
             self.plan.append(e)
         self.T = T
-        # two dY buffers: the filter gradient of layer L runs on a side stream while the main stream already
-        # prepares dY of layer L-1 (see backward)
-        self.dYs = [torch.empty(max_dy, dtype=self.g_dtype, device=device) for _ in range(2)]
-        self.dY = self.dYs[0]
-        # ... or one dY buffer per layer (default): the main chain then never waits for the side stream, the captured step is one
-        # linear chain plus a side chain with fork edges only, and the graph executor keeps the chain on one hardware queue
-        # (with the two alternating buffers the joins spread it over three queues: ~17 us per cross-queue hop, 2-3 per layer)
-        self.dy_per_layer = os.environ.get("MANTLE_DY_PER_LAYER", "1") != "0" and self.overlap_wgrad != 0
-        if self.dy_per_layer:
-            for e in self.plan:
-                if e["node"].kind == "conv":
-                    o = T[e["node"].out]
-                    e["dY"] = torch.empty(N * e["coutp"] * o.H * o.W, dtype=self.g_dtype, device=device)
+        # one output-gradient buffer for every layer: backward is one stream, so a layer's filter- and input-gradient
+        # launches have read it before the next layer down writes its own
+        self.dY = torch.empty(max_dy, dtype=self.g_dtype, device=device)
         self.convs = [e for e in self.plan if e["node"].kind == "conv" and not e["node"].learned]
-        self.side = torch.cuda.Stream(device=device)
-        # events of the two-stream backward, created once (none is created inside a graph capture)
-        self._events = [torch.cuda.Event() for _ in range(2 * len(self.plan) + 2)]
         last = self.plan[-1]
         assert last["node"].kind == "conv", "graph must end in a conv node"
         self.final_plain = last["node"].post == L.POST_NONE
@@ -647,57 +650,32 @@ class Engine:
         self.shape = (N, H, W, str(device))
 
     # -------------------------------------------------------------- learned padding (BoundaryLearnedConvolution2D)
-    LBANKS = ("conv", "conv_top_left", "conv_top_right", "conv_bottom_left", "conv_bottom_right", "conv_top", "conv_bottom",
-              "conv_left", "conv_right")
-
-    def _plan_learned(self, node, srcs, T, cb8, cb8g, f32, N, device):
+    def _plan_learned(self, node, shape, s, o, cb8, cb8g, f32):
         """Nine bias-free valid convolutions on the library's conv kernels, the strips cut / the frame assembled with
         mc_rect_copy (reference pytorch_networks_convae.py:1022-1065).  The gradient w.r.t. the input needs no padded
         domain: the adjoint of a valid convolution is exactly input-sized."""
-        assert len(srcs) == 1, "learned padding takes one source tensor"
-        s, o = srcs[0], T[node.out]
-        h, w, k = s.H, s.W, node.k
-        pad_x = k + 1 + (node.bc_x - 1) if k == 5 else k + (node.bc_x - 1)
-        pad_y = k + 1 + (node.bc_y - 1) if k == 5 else k + (node.bc_y - 1)
-        fx, fy, mh, mw = pad_x - k + 1, pad_y - k + 1, h - k + 1, w - k + 1
-        if mh < 1 or mw < 1 or pad_x > w or pad_y > h:
-            raise ValueError(f"{node.name}: input {h}x{w} too small for learned padding")
-        ho, wo = mh + 2 * fy, mw + 2 * fx
-        o.H, o.W = ho, wo
-        regs = {"conv": (0, 0, h, w, fy, fx),
-                "conv_left": (0, 0, h, pad_x, fy, 0), "conv_right": (0, w - pad_x, h, pad_x, fy, fx + mw),
-                "conv_bottom": (h - pad_y, 0, pad_y, w, 0, fx), "conv_top": (0, 0, pad_y, w, fy + mh, fx),
-                "conv_bottom_left": (h - pad_y, 0, pad_y, pad_x, 0, 0),
-                "conv_bottom_right": (h - pad_y, w - pad_x, pad_y, pad_x, 0, fx + mw),
-                "conv_top_left": (0, 0, pad_y, pad_x, fy + mh, 0), "conv_top_right": (0, w - pad_x, pad_y, pad_x, fy + mh, fx + mw)}
+        N, u8 = self.N, dict(dtype=torch.uint8, device=self.device)
         banks = {}
-        for name, (sy, sx, sh, sw, dy, dx) in regs.items():
-            d = L.ConvDesc(N, sh, sw, s.C, 0, node.c_out, k, 0, L.PAD_MODES["zeros"], self.mc_dtype, node.sym_h, 0, 0)
-            rh, rw = sh - k + 1, sw - k + 1
-            dd = L.ConvDesc(N, rh, rw, node.c_out, 0, s.C, k, k - 1, 0, self.mc_gdtype, 0, 0, 0)
+        for name, (reg, d, dd) in shape.banks.items():
             if L.call("mc_conv_tiles", C.byref(d)) <= 0:
                 raise L.MantleHipError(f"unsupported convolution configuration for {node.name}{name}")
-            u8 = dict(dtype=torch.uint8, device=device)
-            banks[name] = dict(desc=d, ddesc=dd, reg=(sy, sx, sh, sw, dy, dx), rh=rh, rw=rw,
+            sh, sw, rh, rw = reg[2], reg[3], dd.h, dd.w           # (dd.h x dd.w: the valid convolution's output)
+            banks[name] = dict(desc=d, ddesc=dd, reg=reg, rh=rh, rw=rw,
                                S=None if name == "conv" else cb8(s.C, sh, sw), R=cb8(node.c_out, rh, rw),
                                dR=cb8g(node.c_out, rh, rw), dS=cb8g(s.C, sh, sw),
                                bank=torch.empty(L.call("mc_packed_weight_bytes", C.byref(d), 0), **u8),
                                dbank=torch.empty(L.call("mc_packed_weight_bytes", C.byref(d), 1), **u8),
                                wpart=torch.empty(L.call("mc_wgrad_partial_bytes", C.byref(d)), **u8))
         coutp = ((node.c_out + 7) // 8) * 8
-        tiles = min(64, ho)
-        e = dict(node=node, banks=banks, tiles=tiles, coutp=coutp, Y=cb8(node.c_out, ho, wo),
-                 part=torch.empty((N, tiles, coutp, 2), **f32), need_dgrad=s.requires_grad, dxl=cb8g(s.C, h, w), desc=None)
-        o.buf = cb8(node.c_out, ho, wo) if node.post != L.POST_NONE else e["Y"]
+        tiles = min(64, o.H)
+        e = dict(node=node, banks=banks, tiles=tiles, coutp=coutp, Y=cb8(node.c_out, o.H, o.W),
+                 part=torch.empty((N, tiles, coutp, 2), **f32), need_dgrad=s.requires_grad, dxl=cb8g(s.C, s.H, s.W), desc=None)
+        o.buf = cb8(node.c_out, o.H, o.W) if node.post != L.POST_NONE else e["Y"]
         if node.post == L.POST_GN_ACT:
             e["stats"] = torch.empty((N, node.groups, 2), **f32)
-            e["gblocks"] = L.call("mc_gn_bwd_blocks", ho, wo)
+            e["gblocks"] = L.call("mc_gn_bwd_blocks", o.H, o.W)
             e["gpart"] = torch.empty((N, e["gblocks"], coutp, 2), **f32)
             e["m12"] = torch.empty((N, node.groups, 2), **f32)
-        if node.pool > 1:
-            p = T[node.pooled]
-            p.H, p.W = ho // node.pool, wo // node.pool
-            p.buf = cb8(node.c_out, p.H, p.W)
         return e
 
     def _learned_forward(self, e, src, params, need_part, st):
@@ -773,18 +751,9 @@ class Engine:
         st = L.stream()
         g, T = self.g, self.T
         act = L.ACTS[g.act]
-        if self.overlap_wgrad or self.overlap_pack:
-            # filter banks are packed on the side stream while the input is converted on the main one
-            main = torch.cuda.current_stream()
-            self.side.wait_stream(main)
-            with torch.cuda.stream(self.side):
-                self._pack_all_banks(params, L.stream())
         L.call("mc_pack_nchw", L.ptr(x), N, g.c_in, Ci, H, W, g.in_pad_w, self.mode, L.ptr(chan_scale), self.mc_dtype,
                L.ptr(T[0].buf), st)
-        if self.overlap_wgrad or self.overlap_pack:
-            main.wait_stream(self.side)
-        else:
-            self._pack_all_banks(params, st)
+        self._pack_all_banks(params, st)
         for e in self.plan:
             node = e["node"]
             if node.kind == "pool":
@@ -895,15 +864,8 @@ class Engine:
         act = L.ACTS[g.act]
         for t in T.values():
             t.gsrcs = []
-        # Two-stream backward: the filter-gradient kernels (x, dY -> dW) of a layer depend only on that layer's dY,
-        # so they run on `side` while `main` continues with the input gradient and the next layer's GroupNorm
-        # backward.  dY alternates between two buffers; main waits for the side stream before reusing one.
-        main = torch.cuda.current_stream()
-        self.side.wait_stream(main)
-        wg_done = [None, None]
+        dY = self.dY                                         # every layer's output gradient (see configure)
         gp_jobs = []                                         # GroupNorm parameter gradients of the one-launch layers
-        k = 0
-        evi = 0
         fo = T[self.plan[-1]["node"].out]
         mean = None
         if g.subtract_mean:
@@ -913,7 +875,7 @@ class Engine:
                 L.call("mc_sum_hw", L.ptr(gout), N * g.c_out, self.out_h * self.out_w, 1.0 / (fo.H * fo.W),
                        L.ptr(self.gmean), st)
             mean = self.gmean
-        gdst = (self.plan[-1]["dY"] if self.dy_per_layer else self.dYs[0]) if self.final_plain else self.dOut
+        gdst = dY if self.final_plain else self.dOut
         L.call("mc_pack_grad_nchw", L.ptr(gout), N, g.c_out, fo.H, fo.W, g.crop_w, L.ptr(mean), self.mc_gdtype,
                L.ptr(gdst), st)
         if not self.final_plain:
@@ -951,7 +913,7 @@ class Engine:
                 s, o = T[node.src], T[node.out]
                 assert len(o.gsrcs) == 1, "an upsampled tensor feeds exactly one conv"
                 (iy, wy, tys, tyj, tyw), (_, _, txs, txj, txw) = e["tabs"]
-                if "bws" not in e and e["maxtaps"][1] <= 12 and BICUBIC_WALK:
+                if "bws" not in e and e["maxtaps"][1] <= 12:
                     L.call("mc_bicubic_bwd_walk", C.byref(o.gsrcs[0]), N, s.C, s.H, s.W, o.H, o.W, L.ptr(iy), L.ptr(wy), L.ptr(tys),
                            L.ptr(tyj), L.ptr(txs), L.ptr(txj), L.ptr(txw), e["maxtaps"][1], self.mc_gdtype, L.ptr(e["dsrc"]), st)
                 elif "bws" in e:
@@ -966,9 +928,6 @@ class Engine:
             d = e["desc"]
             o = T[node.out]
             srcs = [T[i] for i in node.srcs]
-            dY = e["dY"] if self.dy_per_layer else self.dYs[k & 1]
-            if not self.dy_per_layer and wg_done[k & 1] is not None:
-                main.wait_event(wg_done[k & 1])          # the side stream has finished reading this dY buffer
             if node.post != L.POST_NONE and "dz" in e:
                 # dz = dA * act'(z) and its partial sums were produced by the consumer's input-gradient launch
                 assert not o.gsrcs, f"{node.name}: fused dz and separate gradient sources"
@@ -1019,31 +978,9 @@ class Engine:
                            self.mc_dtype, g0, g1, L.ptr(dY), st)
             if node.learned:
                 self._learned_backward(e, srcs[0], dY, params, grads, st)
-                k += 1
                 continue
             x0, x1, pro = self._sources(srcs)
-            side = self.side if (self.overlap_wgrad == 1 or (self.overlap_wgrad == 2 and o.H * o.W <= 128 * 128)) else main
-            wg_done[k & 1] = None
-            if side is not main:
-                ev = self._events[evi]
-                evi += 1
-                ev.record(main)                           # dY of this layer is complete
-                side.wait_event(ev)
-            with torch.cuda.stream(side):
-                ss = L.stream()
-                L.call("mc_conv2d_wgrad_fused", C.byref(d), x0, x1, pro, L.ptr(dY), L.ptr(e["wpart"]), ss)
-                if self.wfin_per_layer and side is not main:
-                    # combine this layer's partial slabs right away on the side stream (hidden under the main chain)
-                    L.call("mc_conv2d_wgrad_finalize", C.byref(d), L.ptr(e["wpart"]), L.ptr(grads[node.name + "weight"]),
-                           L.ptr(grads[node.name + "bias"]), ss)
-                    e["_wfin_done"] = True
-                else:
-                    e["_wfin_done"] = False
-                if side is not main:
-                    wg_done[k & 1] = self._events[evi]
-                    evi += 1
-                    wg_done[k & 1].record(side)
-            k += 1
+            L.call("mc_conv2d_wgrad_fused", C.byref(d), x0, x1, pro, L.ptr(dY), L.ptr(e["wpart"]), st)
             if e["need_dgrad"]:
                 dxp = e["dxp"]
                 pe = e.get("epi")
@@ -1076,20 +1013,18 @@ class Engine:
                         L.call("mc_fold_padded", L.ptr(buf), N, s.C, s.H, s.W, node.pad, self.mode, self.mc_gdtype, st)
                 for s, buf in live:
                     s.gsrcs.append(L.GradSrc(L.ptr(buf), L.GSRC_PADFOLD, node.pad, self.mode, 1, s.H, s.W))
-        main.wait_stream(self.side)
         if gp_jobs:
             n = len(gp_jobs)
             L.call("mc_gn_param_grads_batched", (C.c_void_p * n)(*[j[0] for j in gp_jobs]), (C.c_int32 * n)(*([N] * n)),
                    (C.c_int32 * n)(*[j[1] for j in gp_jobs]), (C.c_void_p * n)(*[j[2] for j in gp_jobs]),
                    (C.c_void_p * n)(*[j[3] for j in gp_jobs]), n, st)
         # one launch combines every layer's partial slabs, folds mirrored filters and accumulates into the gradients
-        todo = [e for e in self.convs if not e.get("_wfin_done")]
-        n = len(todo)
+        n = len(self.convs)
         if n:
-            descs = (L.ConvDesc * n)(*[e["desc"] for e in todo])
-            parts = (C.c_void_p * n)(*[L.ptr(e["wpart"]) for e in todo])
-            dws = (C.c_void_p * n)(*[L.ptr(grads[e["node"].name + "weight"]) for e in todo])
-            dbs = (C.c_void_p * n)(*[L.ptr(grads[e["node"].name + "bias"]) for e in todo])
+            descs = (L.ConvDesc * n)(*[e["desc"] for e in self.convs])
+            parts = (C.c_void_p * n)(*[L.ptr(e["wpart"]) for e in self.convs])
+            dws = (C.c_void_p * n)(*[L.ptr(grads[e["node"].name + "weight"]) for e in self.convs])
+            dbs = (C.c_void_p * n)(*[L.ptr(grads[e["node"].name + "bias"]) for e in self.convs])
             L.call("mc_conv2d_wgrad_finalize_batched", descs, parts, dws, dbs, n, st)
 
     def _pack_all_banks(self, params, st):

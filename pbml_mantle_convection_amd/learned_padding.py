@@ -17,23 +17,10 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
+from .engine import BANKS, learned_regions
 from .symmetric_layers_torch import SymmetricConv2d
 
-BANKS = ("conv", "conv_top_left", "conv_top_right", "conv_bottom_left", "conv_bottom_right", "conv_top", "conv_bottom",
-         "conv_left", "conv_right")
 _DT = {"fp32": (L.MC_F32, torch.float32), "bf16": (L.MC_BF16, torch.bfloat16)}
-
-
-def _regions(H, W, k):
-    """name -> (input sy, sx, sh, sw, output dy, dx) for bc = 1."""
-    pad = k + 1 if k == 5 else k
-    f = pad - k + 1
-    mh, mw = H - k + 1, W - k + 1
-    return f, {
-        "conv_left": (0, 0, H, pad, f, 0), "conv_right": (0, W - pad, H, pad, f, f + mw),
-        "conv_bottom": (H - pad, 0, pad, W, 0, f), "conv_top": (0, 0, pad, W, f + mh, f),
-        "conv_bottom_left": (H - pad, 0, pad, pad, 0, 0), "conv_bottom_right": (H - pad, W - pad, pad, pad, 0, f + mw),
-        "conv_top_left": (0, 0, pad, pad, f + mh, 0), "conv_top_right": (0, W - pad, pad, pad, f + mh, f + mw)}
 
 
 class _Plan:
@@ -41,7 +28,8 @@ class _Plan:
         self.key = (N, H, W, precision, str(device))
         self.N, self.H, self.W, self.c_i, self.c_o, self.k = N, H, W, c_i, c_o, k
         self.mc, self.td = _DT[precision]
-        self.f, self.regions = _regions(H, W, k)
+        self.f, _, _, _, regions = learned_regions(H, W, k)          # (fy = fx for bc = 1)
+        self.regions = {n: r for n, r in regions.items() if n != "conv"}
         if H < 2 * self.f + 1 + (k - 1) or W < 2 * self.f + 1 + (k - 1):
             raise ValueError("input too small for the learned-padding strips")
         dev = device
