@@ -327,6 +327,15 @@ int mc_curl_head_bwd(const float* gu, const float* gv, const float* gt_out, cons
                      int32_t w, float a_bound, float t_lo, float t_hi, float* ga, float* gt_in,
                      int64_t g_batch_stride, int64_t in_batch_stride, float* ws, void* stream);
 
+/* ---- curl head of FluidNet (pytorch_networks_convae.py:1681-1697): a = a_bound * y[:, 0] on an (h+2) x (w+2) field,
+ *      u[i][j] = 0.5 (a[i+2][j+1] - a[i][j+1]), v[i][j] = -0.5 (a[i+1][j+2] - a[i+1][j]) on h x w, no wall fix-up.
+ *      a / ga: (h+2) x (w+2) f32 planes with a batch stride; u, v, gu, gv: [n][h][w].  The backward writes every pixel of
+ *      ga's planes (no memset needed) without atomics or workspace. --- */
+int mc_curl_valid_fwd(const float* a, int32_t n, int32_t h, int32_t w, int64_t in_batch_stride, float a_bound, float* u,
+                      float* v, void* stream);
+int mc_curl_valid_bwd(const float* gu, const float* gv, int32_t n, int32_t h, int32_t w, float a_bound, float* ga,
+                      int64_t g_batch_stride, void* stream);
+
 /* ---- loss (Trainer.loss_fn multigpu.py:122-134; get_loss :250-305) + build-defined momentum -- */
 #define MC_LOSS_SLOTS 16
 enum { MC_S_U_SCALED = 0, MC_S_U_PLAIN, MC_S_V_SCALED, MC_S_V_PLAIN, MC_S_P_PLAIN, MC_S_T_PLAIN,

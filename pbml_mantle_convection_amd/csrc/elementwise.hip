@@ -1667,6 +1667,44 @@ __global__ void k_curl_bwd_stencil(const float* __restrict__ eu, const float* __
   }
 }
 
+// curl head of FluidNet (:1681-1697): the conv stack grew the field to (H+2) x (W+2), so the centred differences of the
+// streamfunction land exactly on H x W -- no wall fix-up, no workspace.  One thread per output pixel, rows along x (coalesced).
+__global__ void __launch_bounds__(256) k_curl_valid_fwd(const float* __restrict__ a_, int H, int W, int64_t abs_, float ab,
+                                                        float* __restrict__ u, float* __restrict__ v) {
+  const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y, n = blockIdx.z;
+  if (x >= W || y >= H) return;
+  const int Wa = W + 2;
+  const float* a = a_ + (size_t)n * abs_;
+  const float uu = 0.5f * (a[(size_t)(y + 2) * Wa + x + 1] - a[(size_t)y * Wa + x + 1]);
+  const float vv = -0.5f * (a[(size_t)(y + 1) * Wa + x + 2] - a[(size_t)(y + 1) * Wa + x]);
+  u[((size_t)n * H + y) * W + x] = ab * uu;
+  v[((size_t)n * H + y) * W + x] = ab * vv;
+}
+
+// adjoint as a gather over the whole (H+2) x (W+2) plane: every pixel of ga is written (no memset), each by one thread from
+// at most four terms in a fixed order (bit-reproducible: no atomics)
+__global__ void __launch_bounds__(256) k_curl_valid_bwd(const float* __restrict__ gu_, const float* __restrict__ gv_, int H, int W,
+                                                        float ab, float* __restrict__ ga_, int64_t gabs) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x, r = blockIdx.y * blockDim.y + threadIdx.y, n = blockIdx.z;
+  if (c >= W + 2 || r >= H + 2) return;
+  const float* gu = gu_ + (size_t)n * H * W;
+  const float* gv = gv_ + (size_t)n * H * W;
+  float acc = 0.f;
+  // u[i][j] = 0.5 (a[i+2][j+1] - a[i][j+1]):  + gu[r-2][c-1], - gu[r][c-1]
+  const int j = c - 1;
+  if (j >= 0 && j < W) {
+    if (r - 2 >= 0 && r - 2 < H) acc += gu[(size_t)(r - 2) * W + j];
+    if (r < H) acc -= gu[(size_t)r * W + j];
+  }
+  // v[i][j] = -0.5 (a[i+1][j+2] - a[i+1][j]):  - gv[r-1][c-2], + gv[r-1][c]
+  const int i = r - 1;
+  if (i >= 0 && i < H) {
+    if (c - 2 >= 0 && c - 2 < W) acc -= gv[(size_t)i * W + c - 2];
+    if (c < W) acc += gv[(size_t)i * W + c];
+  }
+  ga_[(size_t)n * gabs + (size_t)r * (W + 2) + c] = ab * 0.5f * acc;
+}
+
 __global__ void k_clip_fwd(const float* __restrict__ t, int hw, int64_t bs, float lo, float hi, float* __restrict__ o) {
   const int n = blockIdx.y;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < hw; i += gridDim.x * blockDim.x)
@@ -2306,6 +2344,24 @@ int mc_curl_head_bwd(const float* gu, const float* gv, const float* gt_out, cons
   dim3 g2(min(cdiv(h * w, 256), 4096), n);
   hipLaunchKernelGGL(k_curl_bwd_stencil, g2, dim3(256), 0, s, eu, ev, h, w, a_bound, ga, g_batch_stride);
   if (gt_in) hipLaunchKernelGGL(k_clip_bwd, g2, dim3(256), 0, s, gt_out, t_in, h * w, in_batch_stride, g_batch_stride, t_lo, t_hi, gt_in);
+  MC_CHECK_LAUNCH();
+  return MC_OK;
+}
+
+int mc_curl_valid_fwd(const float* a, int32_t n, int32_t h, int32_t w, int64_t in_batch_stride, float a_bound, float* u,
+                      float* v, void* stream) {
+  if (!a || !u || !v || n <= 0 || n > 65535 || h <= 0 || w <= 0 || in_batch_stride < (int64_t)(h + 2) * (w + 2)) return MC_EINVAL;
+  dim3 g(cdiv(w, 64), cdiv(h, 4), n);
+  hipLaunchKernelGGL(k_curl_valid_fwd, g, dim3(64, 4), 0, (hipStream_t)stream, a, h, w, in_batch_stride, a_bound, u, v);
+  MC_CHECK_LAUNCH();
+  return MC_OK;
+}
+
+int mc_curl_valid_bwd(const float* gu, const float* gv, int32_t n, int32_t h, int32_t w, float a_bound, float* ga,
+                      int64_t g_batch_stride, void* stream) {
+  if (!gu || !gv || !ga || n <= 0 || n > 65535 || h <= 0 || w <= 0 || g_batch_stride < (int64_t)(h + 2) * (w + 2)) return MC_EINVAL;
+  dim3 g(cdiv(w + 2, 64), cdiv(h + 2, 4), n);
+  hipLaunchKernelGGL(k_curl_valid_bwd, g, dim3(64, 4), 0, (hipStream_t)stream, gu, gv, h, w, a_bound, ga, g_batch_stride);
   MC_CHECK_LAUNCH();
   return MC_OK;
 }

@@ -237,14 +237,15 @@ def convae_graph(levels, c_i, c_h, c_o, *, act, r_p, use_symm, repeats, f, loss_
     return NetGraph(c_i, int(c_o), ch, nodes, pad_mode=r_p, act=act, divisor=4 ** levels)
 
 
-def newfluidnet_graph(levels, c_i, c_h, c_o, *, act, r_p, use_symm, repeats, f, factor=2) -> NetGraph:
-    """Layer wiring of NewFluidNet.__init__/forward (reference pytorch_networks_convae.py:1215-1346): level l = the input
-    feature map average-pooled l times, `repeats` FluidLayers, bicubic back to the input size; six-way concat with the raw
-    inputs; 3 x 3 head.  The reference re-pools the feature map from scratch for every level; the values are identical to
-    pooling the previous level once more, which is what the graph does."""
+def _fluid_trunk(levels, c_i, c_h, *, act, r_p, use_symm, repeats, f, factor):
+    """The multi-resolution trunk NewFluidNet and FluidNet share (reference pytorch_networks_convae.py:1315-1337 and
+    :1642-1658): level l = the input feature map average-pooled l times, `repeats` FluidLayers, bicubic back to the input
+    size; concat of the levels with the raw inputs.  The reference re-pools the feature map from scratch for every level; the
+    values are identical to pooling the previous level once more, which is what the graph does.  Returns (channels, nodes,
+    tensor id of the concat, new-tensor function)."""
     if c_h % 8:
-        raise NotImplementedError("the HIP path of NewFluidNet needs c_h to be a multiple of 8 (channel-block concat)")
-    learned = r_p == "learned"          # every conv a BoundaryLearnedConvolution2D; the head then uses k = f (reference :1296-1313)
+        raise NotImplementedError("the HIP path of NewFluidNet / FluidNet needs c_h to be a multiple of 8 (channel-block concat)")
+    learned = r_p == "learned"
     ch: Dict[int, int] = {0: c_i}
     nodes = []
     nid = [0]
@@ -279,6 +280,15 @@ def newfluidnet_graph(levels, c_i, c_h, c_o, *, act, r_p, use_symm, repeats, f, 
         outs.append(cur)
     cat = new(c_h * levels + c_i)
     nodes.append(CatNode(outs + [0], cat))
+    return ch, nodes, cat, new
+
+
+def newfluidnet_graph(levels, c_i, c_h, c_o, *, act, r_p, use_symm, repeats, f, factor=2) -> NetGraph:
+    """Layer wiring of NewFluidNet.__init__/forward (reference pytorch_networks_convae.py:1215-1346): the shared trunk
+    (_fluid_trunk), then a 3 x 3 head (k = f with learned padding)."""
+    learned = r_p == "learned"          # every conv a BoundaryLearnedConvolution2D; the head then uses k = f (reference :1296-1313)
+    ch, nodes, cat, new = _fluid_trunk(levels, c_i, c_h, act=act, r_p=r_p, use_symm=use_symm, repeats=repeats, f=f,
+                                       factor=factor)
     hk = f if learned else 3
 
     def hsym(c):
@@ -290,6 +300,33 @@ def newfluidnet_graph(levels, c_i, c_h, c_o, *, act, r_p, use_symm, repeats, f, 
     nodes.append(ConvNode("conv.2.", [o], o2, c_h, hk, hk // 2, hsym(c_h), L.POST_ACT, None, 1, learned=learned))
     o3 = new(c_o)
     nodes.append(ConvNode("conv.3.", [o2], o3, c_o, hk, hk // 2, hsym(c_o), L.POST_NONE, None, 1, learned=learned))
+    return NetGraph(c_i, c_o, ch, nodes, subtract_mean=True, pad_mode="zeros" if learned else r_p, act=act, divisor=1)
+
+
+def fluidnet_graph(levels, c_i, c_h, c_o, *, act, r_p, use_symm, repeats, f, factor=2) -> NetGraph:
+    """Layer wiring of FluidNet.__init__/forward with loss_type 'curl' (reference pytorch_networks_convae.py:1581-1665): the
+    trunk of NewFluidNet, then a head whose first conv grows the field by one pixel on every side, so that the output is
+    (H + 2) x (W + 2) and the curl head's centred differences land on H x W (mc_curl_valid_*).  Learned padding: conv.1 is a
+    k = f BoundaryLearnedConvolution2D called with bc_x = bc_y = 2 (:1660), conv.2 / conv.3 plain learned convs.  Fixed
+    padding: conv.1 is the constructor's 3 x 3 conv with padding (2, 2), conv.2 / conv.3 3 x 3 with padding 1 (the reference's
+    forward passes bc_x / bc_y to that nn.Conv2d and fails)."""
+    learned = r_p == "learned"
+    ch, nodes, cat, new = _fluid_trunk(levels, c_i, c_h, act=act, r_p=r_p, use_symm=use_symm, repeats=repeats, f=f,
+                                       factor=factor)
+    if learned:
+        def head(name, src, c_out, post, gn_name, groups, bc):
+            o = new(c_out)
+            nodes.append(ConvNode(name, [src], o, c_out, f, f // 2, _sym_h(c_out) if use_symm else 0, post, gn_name, groups,
+                                  learned=True, bc_x=bc, bc_y=bc))
+            return o
+    else:
+        def head(name, src, c_out, post, gn_name, groups, bc):
+            o = new(c_out)
+            nodes.append(ConvNode(name, [src], o, c_out, 3, 1 + (bc - 1), 0, post, gn_name, groups))
+            return o
+    o = head("conv.1.", cat, c_h, L.POST_GN_ACT, "gn.0.", int(c_h / 4), 2)
+    o2 = head("conv.2.", o, c_h, L.POST_ACT, None, 1, 1)
+    head("conv.3.", o2, c_o, L.POST_NONE, None, 1, 1)
     return NetGraph(c_i, c_o, ch, nodes, subtract_mean=True, pad_mode="zeros" if learned else r_p, act=act, divisor=1)
 
 

@@ -1,6 +1,6 @@
 """Fused training loss on MI355X: Trainer.loss_fn / get_loss arithmetic (reference
 multigpu.py:122-134, 250-305) plus the build-defined Stokes momentum residual, forward AND
-backward in one pass over the fields (libmantle_hip: mc_loss_* / mc_momentum_* / mc_curl_head_*).
+backward in one pass over the fields (libmantle_hip: mc_loss_* / mc_momentum_* / mc_curl_head_* / mc_curl_valid_*).
 
 `StokesLoss.evaluate` works on raw device buffers (used by the fused trainer, graph-capturable);
 `StokesLoss.__call__` is the autograd-visible form used by Trainer.get_loss.
@@ -23,7 +23,7 @@ OUT_NAMES = ("loss", "loss_true_u", "loss_true_v", "loss_p", "loss_T", "mass", "
 class StokesLoss:
     def __init__(self, p_pred: bool, loss_type: str, loss_scale: bool = False, loss_derivative: bool = False,
                  norm: str = "l1", lambda_mom: float = 0.0, inv_h: float = 126.0, ra: float = 1.0,
-                 a_bound: float = 10.0, t_grad: bool = True, has_T: bool = True):
+                 a_bound: float = 10.0, t_grad: bool = True, has_T: bool = True, curl_valid: bool = False):
         if loss_type not in L.LOSS_TYPES:
             raise ValueError(f"loss_type must be one of {list(L.LOSS_TYPES)}")
         if norm not in ("l1", "l2"):
@@ -37,6 +37,12 @@ class StokesLoss:
         self.has_T = bool(has_T)
         if not self.has_T and self.lambda_mom != 0.0:
             raise ValueError("the momentum residual needs the temperature output (Unet); use lambda_mom = 0 with has_T = False")
+        # curl_valid: FluidNet (reference pytorch_networks_convae.py:1681-1697): the network output is the streamfunction on the
+        # grown (H+2) x (W+2) field and u, v are its plain centred differences on the H x W grid of the truth
+        # (mc_curl_valid_fwd -> mc_loss_fwd_bwd -> mc_curl_valid_bwd)
+        self.curl_valid = bool(curl_valid)
+        if self.curl_valid and (loss_type != "curl" or self.has_T or self.p_pred):
+            raise ValueError("curl_valid is FluidNet's head: loss_type 'curl', has_T = False, p_pred = False")
         self._shape = None
 
     # ------------------------------------------------------------------
@@ -53,11 +59,12 @@ class StokesLoss:
         self.sums = torch.zeros(L.LOSS_SLOTS, dtype=torch.float64, device=dev)
         self.out8 = torch.zeros(8, **f32)
         self.mm = torch.zeros((N, 3, 2), **f32)
-        self.gy = torch.zeros((N, Cc, H, W), **f32)
+        g2 = 2 if self.curl_valid else 0                     # (the gradient w.r.t. the grown field)
+        self.gy = torch.zeros((N, Cc, H + g2, W + g2), **f32)
         if self.loss_type == "curl":
             self.cu, self.cv, self.cT = (torch.empty((N, H, W), **f32) for _ in range(3))
             self.gcu, self.gcv, self.gcT = (torch.empty((N, H, W), **f32) for _ in range(3))
-            self.curl_ws = torch.empty(2 * N * (H - 2) * (W - 2), **f32)
+            self.curl_ws = None if self.curl_valid else torch.empty(2 * N * (H - 2) * (W - 2), **f32)
         self.gsum_blocks, self.gsum_part = 0, None
         if self.fusable() and Cc <= 4:
             # per-block spatial sums of the gradient planes (the adjoint of the network's mean subtraction takes its means
@@ -88,8 +95,8 @@ class StokesLoss:
 
     def evaluate(self, y: Optional[torch.Tensor], uvp: torch.Tensor, yc: Optional[torch.Tensor] = None,
                  paras: Optional[torch.Tensor] = None, scaler: Optional[torch.Tensor] = None, cb8=None):
-        """y: network output [N, C, H, W] f32 (Unet.features / ConvAE output); uvp: truth
-        [N, 3|4, H, W] f32.  Returns (out8, gy): out8 = (loss, true_u, true_v, loss_p, loss_T, mass,
+        """y: network output [N, C, H, W] f32 (Unet.features / ConvAE output; [N, C, H + 2, W + 2] with curl_valid);
+        uvp: truth [N, 2|3|4, H, W] f32.  Returns (out8, gy): out8 = (loss, true_u, true_v, loss_p, loss_T, mass,
         momentum, 0) on device; gy = d(loss)/d(y).
         cb8 (only with `fusable()`): (buf, mean, crop, (N, C, H, W)) -- the last convolution's f32 output in the CB8 layout
         [N][ceil(C / 8)][H][W + 2 crop][8] and its per-(sample, channel) spatial means; y is not read then (may be None)."""
@@ -104,6 +111,8 @@ class StokesLoss:
             if y.dtype != torch.float32 or not y.is_contiguous():
                 raise RuntimeError("y must be contiguous f32")
             N, Cc, H, W = y.shape
+            if self.curl_valid:
+                H, W = H - 2, W - 2
             dev = y.device
         if uvp.dtype != torch.float32 or not uvp.is_contiguous():
             uvp = uvp.float().contiguous()
@@ -147,7 +156,15 @@ class StokesLoss:
             L.call("mc_loss_finalize", C.byref(d), L.ptr(self.sums), L.ptr(self.out8), st)
             return self.out8, self.gy
         yb = y.data_ptr()
-        if self.loss_type == "curl" and not self.has_T:
+        if self.curl_valid:
+            # FluidNet: channel 0 = streamfunction on (H+2) x (W+2)
+            if Cc > 1:
+                self.gy.zero_()
+            L.call("mc_curl_valid_fwd", yb, N, H, W, Cc * (H + 2) * (W + 2), self.a_bound, L.ptr(self.cu), L.ptr(self.cv), st)
+            u, v, T, pbs = self.cu.data_ptr(), self.cv.data_ptr(), None, HW
+            gu, gv, gT = self.gcu.data_ptr(), self.gcv.data_ptr(), None
+            p = gp = None
+        elif self.loss_type == "curl" and not self.has_T:
             # NewFluidNet: channel 0 = streamfunction, 1 = p  (reference pytorch_networks_convae.py:1360-1369)
             self.gy.zero_()
             L.call("mc_curl_head_fwd", yb, None, N, H, W, Cc * HW, self.a_bound, 0.0, 0.0, L.ptr(self.cu), L.ptr(self.cv),
@@ -196,7 +213,9 @@ class StokesLoss:
                    L.ptr(self.sums), L.ptr(self.sx), L.ptr(self.sy), L.ptr(self.eta), st)
             L.call("mc_momentum_adjoint", C.byref(d), T, pbs, ppbs, L.ptr(self.eta), L.ptr(paras), L.ptr(scaler),
                    L.ptr(self.sx), L.ptr(self.sy), gu, gv, gp, gT, st)
-        if self.loss_type == "curl" and not self.has_T:
+        if self.curl_valid:
+            L.call("mc_curl_valid_bwd", gu, gv, N, H, W, self.a_bound, gb, Cc * (H + 2) * (W + 2), st)
+        elif self.loss_type == "curl" and not self.has_T:
             L.call("mc_curl_head_bwd", gu, gv, None, None, N, H, W, self.a_bound, 0.0, 0.0, gb, None, Cc * HW, Cc * HW,
                    L.ptr(self.curl_ws), st)
         elif self.loss_type == "curl":

@@ -30,7 +30,7 @@ from . import _lib as L
 from .datasetio import *  # noqa: F401,F403  (reference does the same star import)
 from .hipnet import FlatParams
 from .losses import StokesLoss
-from .pytorch_networks_convae import ConvAE, NewFluidNet, Unet, count_parameters
+from .pytorch_networks_convae import ConvAE, FluidNet, NewFluidNet, Unet, count_parameters
 
 
 def ddp_setup(rank, world_size, master_port, backend: Optional[str] = None):
@@ -98,9 +98,9 @@ class Trainer:
                  optimizer: torch.optim.Optimizer, scheduler, gpu_id: int, save_every: int, nn_dir, p_pred=False,
                  debug=False, network="fluidnet", loss_scale=False, loss_derivative=False, roll_forward=1, epoch=0,
                  loss_type="curl", *, norm="l1", lambda_mom=0.0, precision=None, use_graph=False, log_every=100):
-        if network not in ("unet", "iunet", "convae", "newfluidnet"):
-            raise NotImplementedError(f"network={network!r}: the HIP path covers 'unet', 'convae' and 'newfluidnet' "
-                                      "(SURVEY.md §8f row N1; the older FluidNet trunk is not built)")
+        if network not in ("unet", "iunet", "convae", "newfluidnet", "fluidnet", "ifluidnet"):
+            raise NotImplementedError(f"network={network!r}: the HIP path covers 'unet' / 'iunet', 'convae', 'newfluidnet' and "
+                                      "'fluidnet' / 'ifluidnet'")
         fluid = "fluidnet" in network          # the reference's `"fluidnet" in self.net` branch of get_loss (:138)
         if fluid and lambda_mom != 0.0:
             raise NotImplementedError("the momentum residual needs the temperature output of the Unet")
@@ -140,7 +140,8 @@ class Trainer:
         a_bound = getattr(self.model_uvp, "a_bound", 10.0)
         self.loss = StokesLoss(p_pred if network != "convae" else False,
                                loss_type if network != "convae" else "mae", loss_scale, loss_derivative, norm=norm,
-                               lambda_mom=lambda_mom, a_bound=a_bound, has_T=not fluid)
+                               lambda_mom=lambda_mom, a_bound=a_bound, has_T=not fluid,
+                               curl_valid=isinstance(self.model_uvp, FluidNet))   # (u, v on H x W from an (H+2) x (W+2) output)
         if network == "convae" or fluid:
             self.chan_scale = None                    # these nets see gVTp as it is (reference :139)
         else:
@@ -452,7 +453,7 @@ class Trainer:
 
 # --------------------------------------------------------------------------------------------------
 def build_model(network, levels, c_i, c_h, c_o, rank, act_fn, r_p, loss_type, use_symm, repeats, kernel,
-                use_skip=False, p_pred=False, spectral_conv=False, dilation=1, a_bound=10, blurr=False, dropout=0.0):
+                use_skip=False, p_pred=False, spectral_conv=False, dilation=1, a_bound=10, blurr=False, dropout=0.0, factor=2):
     """Model construction of load_train_objs (reference :492-609) without the `.double()` (the HIP path
     computes in f32 or bf16 with f32 master weights)."""
     dev = torch.device("cuda", rank) if isinstance(rank, int) else rank
@@ -468,7 +469,11 @@ def build_model(network, levels, c_i, c_h, c_o, rank, act_fn, r_p, loss_type, us
         return NewFluidNet(levels, c_i, c_h, c_o, dev, act_fn, r_p, loss_type, use_symm=use_symm, dilation=dilation,
                            a_bound=a_bound, repeats=repeats, use_skip=use_skip, f=kernel, p_pred=p_pred,
                            spectral_conv=spectral_conv, blurr=blurr, drop_rate=dropout)
-    raise NotImplementedError(f"network={network!r} is outside the HIP path (unet, convae, newfluidnet)")
+    if network in ("fluidnet", "ifluidnet"):            # (the reference builds the same FluidNet for both, :492)
+        return FluidNet(levels, c_i, c_h, c_o, dev, act_fn, r_p, loss_type, use_symm=use_symm, dilation=dilation,
+                        a_bound=a_bound, repeats=repeats, use_skip=use_skip, f=kernel, p_pred=p_pred,
+                        spectral_conv=spectral_conv, blurr=blurr, drop_rate=dropout, factor=factor)
+    raise NotImplementedError(f"network={network!r} is outside the HIP path (unet, convae, newfluidnet, fluidnet)")
 
 
 def parse_restart_log(nn_dir, milestones):
@@ -495,7 +500,7 @@ def load_train_objs(rank, world_size, nn_dir, data_dir, levels, c_i, c_h, c_o, a
     if advect:
         raise NotImplementedError("advect=True (ADNet) is out of scope")
     model_uvp = build_model(network, levels, c_i, c_h, c_o, rank, act_fn, r_p, loss_type, use_symm, repeats, kernel,
-                            use_skip, p_pred, spectral_conv, dilation, a_bound, blurr, dropout)
+                            use_skip, p_pred, spectral_conv, dilation, a_bound, blurr, dropout, factor=factor)
     print(count_parameters(model_uvp))
     if restart:
         epoch, start_lr, milestones = parse_restart_log(nn_dir, milestones)

@@ -2,7 +2,7 @@
 (reference pytorch_networks_convae.py; ConvAE from .ipynb_checkpoints/pycold-checkpoint.py:989-1115),
 executed by the HIP engine on MI355X.
 
-Only the modules on the training hot path are provided (FluidLayer, Unet, ConvAE) plus the
+Only the modules on the training hot path are provided (FluidLayer, Unet, ConvAE, NewFluidNet, FluidNet) plus the
 small field helpers the reference exports from this module.  Everything numeric inside
 forward()/backward() runs in libmantle_hip kernels; there is no CPU path.
 """
@@ -16,7 +16,7 @@ import torch.nn.functional as F
 import torch.optim as optim
 
 from . import _lib as L
-from .engine import convae_graph, newfluidnet_graph, single_layer_graph, unet_graph
+from .engine import convae_graph, fluidnet_graph, newfluidnet_graph, single_layer_graph, unet_graph
 from .hipnet import HipNetMixin
 from .learned_padding import BoundaryLearnedConvolution2D   # noqa: F401  (reference :802-1065)
 from .symmetric_layers_torch import SymmetricConv2d
@@ -373,6 +373,105 @@ class NewFluidNet(nn.Module, HipNetMixin):
             u, v = _CurlUV.apply(y, self.a_bound)
             return u, v, (y[:, 1] if self.p_pred else None)
         raise ValueError(self.loss_type)
+
+
+# --------------------------------------------------------------------------------------------------
+# FluidNet (reference :1392-1697): the NewFluidNet trunk with a head that grows the field to (H+2) x (W+2)
+# --------------------------------------------------------------------------------------------------
+class _CurlValid(torch.autograd.Function):
+    """u, v on H x W from the streamfunction channel of an (H+2) x (W+2) output (:1681-1697): plain centred differences,
+    no wall fix-up (mc_curl_valid_fwd / mc_curl_valid_bwd)."""
+
+    @staticmethod
+    def forward(ctx, y, a_bound):
+        N, Cc, Hy, Wy = y.shape
+        H, W = Hy - 2, Wy - 2
+        y = y.contiguous()
+        u = torch.empty((N, H, W), dtype=torch.float32, device=y.device)
+        v = torch.empty_like(u)
+        L.call("mc_curl_valid_fwd", L.ptr(y), N, H, W, Cc * Hy * Wy, float(a_bound), L.ptr(u), L.ptr(v), L.stream())
+        ctx.shape, ctx.a_bound = (N, Cc, Hy, Wy), float(a_bound)
+        return u, v
+
+    @staticmethod
+    def backward(ctx, gu, gv):
+        N, Cc, Hy, Wy = ctx.shape
+        dev = gu.device if gu is not None else gv.device
+        # the kernel writes every pixel of channel 0; only further channels need zeros
+        gy = (torch.zeros if Cc > 1 else torch.empty)((N, Cc, Hy, Wy), dtype=torch.float32, device=dev)
+        gu = (gu if gu is not None else torch.zeros((N, Hy - 2, Wy - 2), device=dev)).contiguous().float()
+        gv = (gv if gv is not None else torch.zeros((N, Hy - 2, Wy - 2), device=dev)).contiguous().float()
+        L.call("mc_curl_valid_bwd", L.ptr(gu), L.ptr(gv), N, Hy - 2, Wy - 2, ctx.a_bound, L.ptr(gy), Cc * Hy * Wy, L.stream())
+        return gy, None
+
+
+class FluidNet(nn.Module, HipNetMixin):
+    """The older multi-resolution surrogate (`-net fluidnet`, the CLI default): NewFluidNet's trunk, then a head whose first
+    conv grows the field by one pixel per side so that the streamfunction's centred differences land on the input grid.
+    Same constructor, module tree and state_dict keys as the reference; forward returns (u, v, None).
+
+    Built for loss_type 'curl' with p_pred = False, the configuration the reference trains (network_lists.ipynb).  With
+    fixed padding the head is the constructor's 3 x 3 padding-2 conv (the reference's forward fails there).
+    The levels are upsampled to the input's size instead of the reference's hard-coded 128 x 506."""
+
+    def __init__(self, levels: int, c_i: int, c_h: int, c_o: int, device=None, act_fn: str = "selu", r_p="zeros",
+                 loss_type="mae", use_symm=False, dilation=1, a_bound=4.0, use_cosine=False, repeats=3, use_skip=False,
+                 f=3, p_pred=True, spectral_conv=False, blurr=False, drop_rate=0.0, factor=2):
+        super().__init__()
+        _check_common(act_fn, r_p, dilation, drop_rate, spectral_conv, blurr)
+        if loss_type in ("mae", "mass"):
+            raise NotImplementedError(f"FluidNet with loss_type={loss_type!r} fails in the reference (its forward skips conv.1, so "
+                                      "GroupNorm sees c_h * levels + c_i channels); only 'curl' is built")
+        if loss_type != "curl":
+            raise ValueError(loss_type)
+        if p_pred:
+            raise NotImplementedError("FluidNet with loss_type='curl' and p_pred=True fails in the reference (p is (H+2) x (W+2), "
+                                      "the truth H x W); use p_pred=False")
+        # (modules in the reference's registration order, :1470-1640: conv, gn, pool, unpool, act, convs)
+        self.conv = nn.ModuleList()
+        self.gn = nn.ModuleList()
+        self.pool = nn.ModuleList()
+        self.unpool = nn.ModuleList()
+        self.levels, self.loss_type, self.a_bound = levels, loss_type, a_bound
+        self.use_cosine, self.repeats, self.use_skip, self.p_pred = use_cosine, repeats, use_skip, p_pred
+        self.c_h, self.c_i, self.c_o = c_h, c_i, c_o
+        self.blurrer = None
+        self.r_p = "constant" if r_p == "zeros" else r_p
+        self.act = {"selu": nn.SELU, "tanh": nn.Tanh, "elu": nn.ELU, "silu": nn.SiLU, "relu": nn.ReLU, "gelu": nn.GELU}[act_fn]()
+        graph = fluidnet_graph(levels, c_i, c_h, c_o, act=act_fn, r_p=r_p, use_symm=use_symm, repeats=repeats, f=f,
+                               factor=factor)
+
+        def fl(cin, cout):
+            return FluidLayer(cin, cout, act_fn, r_p, use_symm, dilation, f=f, drop_rate=drop_rate)
+
+        self.conv.append(fl(c_i, c_h))
+        self.pool = nn.AvgPool2d((factor, factor), stride=factor)      # (replaces the ModuleList in place, as the reference does)
+        for _ in range(1, levels):
+            self.unpool.append(nn.Upsample(size=(128, 506), mode="bicubic"))
+        self.convs = nn.ModuleList()
+        for l in range(levels):
+            self.convs.append(nn.ModuleList())
+            for r in range(repeats):
+                self.convs[l].append(fl(c_h, c_h))
+        if r_p == "learned":                                                   # reference :1581-1640
+            self.conv.append(BoundaryLearnedConvolution2D(c_h * levels + c_i, c_h, k=f, use_symm=use_symm))
+            self.gn.append(torch.nn.GroupNorm(int(c_h / 4), c_h))
+            self.conv.append(BoundaryLearnedConvolution2D(c_h, c_h, k=f, use_symm=use_symm))
+            self.conv.append(BoundaryLearnedConvolution2D(c_h, c_o, k=f, use_symm=use_symm))
+        else:
+            self.conv.append(nn.Conv2d(c_h * levels + c_i, c_h, kernel_size=3, padding=(2, 2), dilation=dilation, padding_mode=r_p))
+            self.gn.append(torch.nn.GroupNorm(int(c_h / 4), c_h))
+            self.conv.append(nn.Conv2d(c_h, c_h, kernel_size=3, padding=(1, 1), padding_mode=r_p))
+            self.conv.append(nn.Conv2d(c_h, c_o, kernel_size=3, padding=(1, 1), padding_mode=r_p))
+        self._init_hipnet(graph)
+
+    def features(self, inputs):
+        """y - mean_HW(y) on the grown (H+2) x (W+2) field: everything up to the curl head (:1642-1679)."""
+        return self._run_graph(inputs)
+
+    def forward(self, inputs):
+        u, v = _CurlValid.apply(self.features(inputs), self.a_bound)
+        return u, v, None
 
 
 # --------------------------------------------------------------------------------------------------

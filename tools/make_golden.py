@@ -722,10 +722,86 @@ def g19():
     npz("g19_adtime_dataset", **out)
 
 
+# ------------------------------------------------------------------ G22 FluidNet (the CLI's default network)
+def _fluidnet_ref(r_p, seed, wrap=False):
+    """The reference FluidNet of the run list's family, small: 2 levels, c_h 8, one repeat, 5 x 5, curl head, p_pred off.
+    wrap: conv.1 called without the bc_x / bc_y keywords its forward passes (fixed padding: an nn.Conv2d rejects them)."""
+    m = P.FluidNet(2, 7, 8, 1, CPU, "gelu", r_p, "curl", use_symm=True, a_bound=10, repeats=1, f=5, p_pred=False).double()
+    randomize_(m, seed)
+    with torch.no_grad():
+        g_ = torch.Generator().manual_seed(seed + 1)
+        for n, p in m.named_parameters():
+            if n.endswith("learnable_bias"):
+                p.copy_((0.1 * torch.randn(p.shape, generator=g_)).float().double())
+    if wrap:
+        conv1 = m.conv[1]
+
+        class NoBC(torch.nn.Module):
+            def __init__(self):
+                super().__init__()
+                self.c = conv1
+
+            def forward(self, x, bc_x=1, bc_y=1):
+                return self.c(x)
+        m.conv._modules["1"] = NoBC()          # (state_dict keys gain ".c." here only: _fluidnet_sd undoes it)
+    return m
+
+
+def _fluidnet_sd(m, grads=False):
+    """state_dict / parameter gradients under the reference's own names (undoing the NoBC wrapper's '.c.')."""
+    if grads:
+        items = [(k, p.grad) for k, p in m.named_parameters()]
+    else:
+        items = list(m.state_dict().items())
+    return {k.replace("conv.1.c.", "conv.1."): v.detach().float() for k, v in items}
+
+
+def g22():
+    B, H, W = 1, 128, 506                     # (the reference's Upsample modules hard-code 128 x 506)
+    for tag, r_p, seed in (("learned", "learned", 220), ("replicate", "replicate", 225)):
+        m = _fluidnet_ref(r_p, seed, wrap=(r_p != "learned"))
+        x = torch.from_numpy(fields.unet_input(B, H, W, seed + 2, c_i=7)).requires_grad_(True)
+        u, v, p = m(x)
+        assert p is None and tuple(u.shape) == (B, H, W)
+        save = {}
+        # cotangents: fields.smooth_field(B, H, W, seed + 3 / + 4) rounded to f32 (regenerated by the test, not stored: the
+        # learned network's parameters and gradients alone take most of the file size budget)
+        ct = {n: torch.from_numpy(fields.smooth_field(B, H, W, seed + 3 + i).astype(np.float32)).to(f64)
+              for i, n in enumerate("uv")}
+        ((u * ct["u"]).sum() + (v * ct["v"]).sum()).backward()
+        for n, o in (("u", u), ("v", v)):
+            save["out/" + n] = fields.strided_sample(o.detach().numpy(), 20001).astype(np.float32)
+        npz(f"g22_fluidnet_{tag}", cfg=np.array([2, 7, 8, 1, 1, 5, 0, 1]), a_bound=np.array(10.0), r_p=np.array(r_p),
+            dx_sample=fields.strided_sample(x.grad.numpy(), 1021).astype(np.float32), **save,
+            **{"sd/" + k: v for k, v in _fluidnet_sd(m).items()}, **{"grad/" + k: v for k, v in _fluidnet_sd(m, True).items()})
+    # (b) the learned network through the reference's Trainer.get_loss, FluidNet branch (loss_scale = loss_derivative = 1)
+    B = 2
+    m = _fluidnet_ref("learned", 220)
+    ns = _trainer_ns(m, False, True, True, "curl")
+    ns.net = "fluidnet"
+    gVTp = torch.from_numpy(fields.unet_input(B, H, W, 2230, c_i=7))
+    uvp = torch.from_numpy(np.stack([fields.smooth_field(B, H, W, 2231), fields.smooth_field(B, H, W, 2232)], 1))
+    out = G.Trainer.get_loss(ns, gVTp, uvp, None, None, None)
+    out[0].backward()
+    npz("g22_fluidnet_get_loss", losses=np.array([float(o.detach()) for o in out]), cfg=np.array([2, 7, 8, 1, 1, 5, 0, 1, 1, 1]),
+        **{"grad/" + k: v for k, v in _fluidnet_sd(m, True).items()})
+    # (d) module tree and parameter count of the two run-list configs (network_lists.ipynb: -l 5 -f 16|8 -r 6|4 -k 5)
+    out = {}
+    for c_h, reps in ((16, 6), (8, 4)):
+        for r_p in ("learned", "replicate"):
+            m = P.FluidNet(5, 7, c_h, 1, CPU, "gelu", r_p, "curl", use_symm=False, a_bound=10, repeats=reps, f=5, p_pred=False)
+            key = f"{r_p}_{c_h}_{reps}"
+            out[f"modules/{key}"] = np.array([n for n, _ in m.named_children()])
+            out[f"conv_types/{key}"] = np.array([type(c).__name__ for c in m.conv])
+            out[f"keys/{key}"] = np.array(list(m.state_dict().keys()))
+            out[f"shapes/{key}"] = np.array([",".join(map(str, v.shape)) for v in m.state_dict().values()])
+            out[f"count/{key}"] = np.array(P.count_parameters(m))
+    npz("g22_fluidnet_modules", **out)
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     torch.set_num_threads(8)
     only = sys.argv[1:]
-    for fn in (g1, g2, g3, g4, g5, g6, g7, g8, g9, g10, g11, g12, g13, g14, g15, g16, g17, g18, g19, g20, g21):
+    for fn in (g1, g2, g3, g4, g5, g6, g7, g8, g9, g10, g11, g12, g13, g14, g15, g16, g17, g18, g19, g20, g21, g22):
         if not only or fn.__name__ in only:
             fn()
