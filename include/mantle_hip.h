@@ -265,10 +265,17 @@ int mc_gn_param_grads_batched(const float* const* chan_sums, const int32_t* n, c
  * (activation-only layer) dy = dz.  dz is read through a gradient source (MC_GSRC_PADFOLD or MC_GSRC_PLAIN). */
 int mc_gn_bwd_apply_dz(const mc_grad_src* dz, const void* y, int32_t n, int32_t c, int32_t h, int32_t w, int32_t groups,
                        const float* coef, const float* m12_ng2, int32_t dtype, void* dy, void* stream);
-/* ---- torch.cat of more than two operands along channels (NewFluidNet.forward, pytorch_networks_convae.py:1327-1332):
- * out [n][sum of blocks][h][w][8]; every operand but the last must have a multiple of 8 channels. */
+/* ---- torch.cat of up to 12 operands along channels (NewFluidNet.forward, pytorch_networks_convae.py:1327-1332; the Unet's
+ * skip concats): out [n][ceil(sum C / 8)][h][w][8], operand k at channels [sum_{j<k} C_j, + C_k).  Any channel counts; when
+ * every operand but the last is a multiple of 8 the launch is a copy of whole blocks.  The lanes past the last channel are
+ * written as zeros when some operand is not a multiple of 8 (when all are aligned they are copied from the last operand). */
 int mc_concat_cb8(const void* const* srcs, const int32_t* src_c, int32_t n_src, int32_t n, int32_t h, int32_t w,
                   int32_t dtype, void* out, void* stream);
+/* Gradient of one concat operand that does not fill whole blocks of the concatenated tensor: out (plain CB8 [n][ceil(c/8)]
+ * [h][w][8], lanes past c zero) = channels [c_off, c_off + c) of the gradient of the c_total-channel concatenated tensor, read
+ * through g (MC_GSRC_PLAIN or MC_GSRC_PADFOLD, a whole tensor: c8_total == 0, hs x ws == h x w).  dtype: the gradient type. */
+int mc_cat_grad_gather(const mc_grad_src* g, int32_t c_total, int32_t c_off, int32_t c, int32_t n, int32_t h, int32_t w,
+                       int32_t dtype, void* out, void* stream);
 /* out (plain CB8 [n][c/8][h][w][8]) = g0 + g1: materialises the gradient of a tensor with two consumers
  * (the pooled feature maps of NewFluidNet feed a conv AND the next pooling level). */
 int mc_gsrc_sum(const mc_grad_src* g0, const mc_grad_src* g1, int32_t n, int32_t c, int32_t h, int32_t w,

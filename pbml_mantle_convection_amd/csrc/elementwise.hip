@@ -1561,6 +1561,99 @@ __global__ void k_concat_cb8(CatTable t, int C8, int HW, T* __restrict__ out) {
   const int total = HW * (int)(sizeof(T) / 2);                    // 16-byte pieces per plane
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) d[i] = s[i];
 }
+// eight lanes of one (pixel, channel block) as raw bits: U = uint32_t (f32, two 16-byte pieces) or uint16_t (16-bit types,
+// one piece).  Bit moves only, so a concat is exact whatever the values.
+template <typename U> struct Lanes8;
+template <> struct Lanes8<uint32_t> {
+  static __device__ __forceinline__ void ld(const uint32_t* p, uint32_t (&o)[8]) {
+    const uint4 a = *reinterpret_cast<const uint4*>(p), b = *reinterpret_cast<const uint4*>(p + 4);
+    o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w; o[4] = b.x; o[5] = b.y; o[6] = b.z; o[7] = b.w;
+  }
+  static __device__ __forceinline__ void st(uint32_t* p, const uint32_t (&o)[8]) {
+    *reinterpret_cast<uint4*>(p) = make_uint4(o[0], o[1], o[2], o[3]);
+    *reinterpret_cast<uint4*>(p + 4) = make_uint4(o[4], o[5], o[6], o[7]);
+  }
+};
+template <> struct Lanes8<uint16_t> {
+  static __device__ __forceinline__ void ld(const uint16_t* p, uint32_t (&o)[8]) {
+    const uint4 a = *reinterpret_cast<const uint4*>(p);
+    o[0] = a.x & 0xffffu; o[1] = a.x >> 16; o[2] = a.y & 0xffffu; o[3] = a.y >> 16;
+    o[4] = a.z & 0xffffu; o[5] = a.z >> 16; o[6] = a.w & 0xffffu; o[7] = a.w >> 16;
+  }
+  static __device__ __forceinline__ void st(uint16_t* p, const uint32_t (&o)[8]) {
+    *reinterpret_cast<uint4*>(p) = make_uint4(o[0] | (o[1] << 16), o[2] | (o[3] << 16), o[4] | (o[5] << 16), o[6] | (o[7] << 16));
+  }
+};
+// w[i] <- w[i + r] (r > 0) or w[i - |r|] (r < 0), |r| < 8, r uniform across the block: three conditional stages with
+// constant indices, so the lanes stay in registers (a select chain on a runtime index is folded back into an indexed load
+// from a private array, which lands in scratch or LDS)
+template <typename V>
+__device__ __forceinline__ void lane_shift16(V (&w)[16], int r) {
+#pragma unroll
+  for (int s = 4; s >= 1; s >>= 1) {
+    if (r >= s && (r & s)) {
+#pragma unroll
+      for (int i = 0; i + s < 16; ++i) w[i] = w[i + s];
+    } else if (r <= -s && ((-r) & s)) {
+#pragma unroll
+      for (int i = 15; i >= s; --i) w[i] = w[i - s];
+    }
+  }
+}
+
+// torch.cat of operands with any channel counts: operand k holds concat channels [off[k], off[k + 1]).  One thread per
+// (pixel, output block); the block's eight lanes come from at most two source blocks of each operand it overlaps
+// (16-byte loads), the lanes past the last channel are written as zeros.  Which operands and blocks a block reads
+// depends on blockIdx.y only, so every branch is uniform.
+struct CatAnyTable { int n; const void* src[CAT_MAX]; int off[CAT_MAX + 1]; };
+template <typename U>
+__global__ __launch_bounds__(256) void k_concat_cb8_any(CatAnyTable t, int C8, int HW, U* __restrict__ out) {
+  const int n = blockIdx.z, cb = blockIdx.y, lo = cb * 8;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < HW; i += gridDim.x * blockDim.x) {
+    uint32_t v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+    for (int k = 0; k < CAT_MAX; ++k) {                              // (unrolled: the table is indexed by constants)
+      if (k >= t.n) break;
+      const int c = t.off[k + 1] - t.off[k], d = lo - t.off[k];     // local channel of lane j: d + j
+      if (d >= c || d + 8 <= 0) continue;
+      const int sc8 = (c + 7) / 8, sb = max(d, 0) >> 3;
+      const U* s = reinterpret_cast<const U*>(t.src[k]);
+      uint32_t w0[8], w1[8] = {0, 0, 0, 0, 0, 0, 0, 0}, w[16];
+      Lanes8<U>::ld(s + ((size_t)(n * sc8 + sb) * HW + i) * 8, w0);
+      if (sb + 1 < sc8 && min(d + 8, c) > (sb + 1) * 8) Lanes8<U>::ld(s + ((size_t)(n * sc8 + sb + 1) * HW + i) * 8, w1);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) { w[j] = w0[j]; w[8 + j] = w1[j]; }
+      lane_shift16(w, d - sb * 8);                                   // lane j <- local channel d + j
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        if (d + j >= 0 && d + j < c) v[j] = w[j];
+    }
+    Lanes8<U>::st(out + ((size_t)(n * C8 + cb) * HW + i) * 8, v);
+  }
+}
+
+// gradient of one unaligned concat operand: out (plain CB8, c channels) = channels [c_off, c_off + c) of the
+// concatenated tensor's gradient source g (c8t blocks); lanes past c are zeros
+template <typename T>
+__global__ __launch_bounds__(256) void k_cat_grad_gather(mc_grad_src g, int c8t, int c_off, int c, int C8, int H, int W,
+                                                         T* __restrict__ out) {
+  const int n = blockIdx.z, cb = blockIdx.y;
+  const int lo = c_off + cb * 8, sb = lo >> 3, r0 = lo & 7, nv = min(8, c - cb * 8);
+  const bool two = r0 + nv > 8;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < H * W; i += gridDim.x * blockDim.x) {
+    const int y = i / W, x = i - y * W;
+    float a[8] = {0, 0, 0, 0, 0, 0, 0, 0}, b[8] = {0, 0, 0, 0, 0, 0, 0, 0}, w[16], v[8];
+    grad_fetch_add<T>(g, n, sb, y, x, c8t, a);
+    if (two) grad_fetch_add<T>(g, n, sb + 1, y, x, c8t, b);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { w[j] = a[j]; w[8 + j] = b[j]; }
+    lane_shift16(w, r0);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = j < nv ? w[j] : 0.0f;
+    V8<T>::st(out + cb8_index(n, cb, y, x, C8, H, W), v);
+  }
+}
+
 template <typename T>
 __global__ void k_gsrc_sum(mc_grad_src g0, mc_grad_src g1, int C8, int H, int W, T* __restrict__ out) {
   const int n = blockIdx.z, cb = blockIdx.y;
@@ -2150,22 +2243,55 @@ int mc_rect_copy(const void* src, int32_t hs, int32_t ws, int32_t sy, int32_t sx
 int mc_concat_cb8(const void* const* srcs, const int32_t* src_c, int32_t n_src, int32_t n, int32_t h, int32_t w,
                   int32_t dtype, void* out, void* stream) {
   if (!srcs || !src_c || !out || n_src < 1 || n_src > CAT_MAX || n <= 0 || h <= 0 || w <= 0) return MC_EINVAL;
+  bool aligned = true;                                       // every operand but the last fills whole blocks
+  for (int k = 0; k < n_src; ++k) {
+    if (!srcs[k] || src_c[k] <= 0) return MC_EINVAL;
+    if (k < n_src - 1 && (src_c[k] % 8) != 0) aligned = false;
+  }
+  if (dtype != MC_F32 && !mc_is16(dtype)) return MC_EUNSUPPORTED;
+  hipStream_t s = (hipStream_t)stream;
+  if (!aligned) {                                            // operand k starts at channel sum_{j<k} C_j
+    CatAnyTable t;
+    t.n = n_src;
+    t.off[0] = 0;
+    for (int k = 0; k < n_src; ++k) { t.src[k] = srcs[k]; t.off[k + 1] = t.off[k] + src_c[k]; }
+    const int C8 = (t.off[n_src] + 7) / 8;
+    dim3 g(max(1, min(cdiv(h * w, 256), 1024)), C8, n);
+    if (dtype == MC_F32) hipLaunchKernelGGL(k_concat_cb8_any<uint32_t>, g, dim3(256), 0, s, t, C8, h * w, (uint32_t*)out);
+    else hipLaunchKernelGGL(k_concat_cb8_any<uint16_t>, g, dim3(256), 0, s, t, C8, h * w, (uint16_t*)out);
+    MC_CHECK_LAUNCH();
+    return MC_OK;
+  }
   CatTable t;
   t.n = n_src;
   int C8 = 0;
   for (int k = 0; k < n_src; ++k) {
-    if (!srcs[k] || src_c[k] <= 0) return MC_EINVAL;
-    if (k < n_src - 1 && (src_c[k] % 8) != 0) return MC_EUNSUPPORTED;      // only the last operand may end in a partial block
     t.src[k] = srcs[k]; t.c8[k] = (src_c[k] + 7) / 8; t.first[k] = C8;
     C8 += t.c8[k];
   }
   t.first[n_src] = C8;
-  hipStream_t s = (hipStream_t)stream;
   const int per = h * w * (dtype == MC_F32 ? 2 : 1);          // (16-bit types: a plain copy of 16-byte pieces)
   dim3 g(max(1, min(cdiv(per, 256 * 4), 1024)), C8, n);
   if (dtype == MC_F32) hipLaunchKernelGGL(k_concat_cb8<float>, g, dim3(256), 0, s, t, C8, h * w, (float*)out);
   else if (mc_is16(dtype)) hipLaunchKernelGGL(k_concat_cb8<bf16_t>, g, dim3(256), 0, s, t, C8, h * w, (bf16_t*)out);
   else return MC_EUNSUPPORTED;
+  MC_CHECK_LAUNCH();
+  return MC_OK;
+}
+
+int mc_cat_grad_gather(const mc_grad_src* g, int32_t c_total, int32_t c_off, int32_t c, int32_t n, int32_t h, int32_t w,
+                       int32_t dtype, void* out, void* stream) {
+  if (!g || !out || n <= 0 || h <= 0 || w <= 0 || c <= 0 || c_off < 0 || c_total <= 0 || c_off + c > c_total) return MC_EINVAL;
+  int rc;
+  if ((rc = check_gsrc(g))) return rc;
+  if (g->kind != MC_GSRC_PLAIN && g->kind != MC_GSRC_PADFOLD) return MC_EUNSUPPORTED;     // (what a concat's consumer hands it)
+  if (g->c8_total != 0 || g->hs != h || g->ws != w) return MC_EINVAL;
+  if (dtype != MC_F32 && !mc_is16(dtype)) return MC_EUNSUPPORTED;
+  const int C8 = (c + 7) / 8, c8t = (c_total + 7) / 8;
+  dim3 gr(max(1, min(cdiv(h * w, 256), 1024)), C8, n);
+  hipStream_t s = (hipStream_t)stream;
+  if (dtype == MC_F32) hipLaunchKernelGGL(k_cat_grad_gather<float>, gr, dim3(256), 0, s, *g, c8t, c_off, c, C8, h, w, (float*)out);
+  else hipLaunchKernelGGL(k_cat_grad_gather<bf16_t>, gr, dim3(256), 0, s, *g, c8t, c_off, c, C8, h, w, (bf16_t*)out);
   MC_CHECK_LAUNCH();
   return MC_OK;
 }

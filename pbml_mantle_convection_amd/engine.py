@@ -74,7 +74,7 @@ class PoolNode:                 # standalone nn.AvgPool2d(f, stride=f) (floor mo
 
 
 @dataclass
-class CatNode:                  # torch.cat of several tensors along channels (every operand but the last: C % 8 == 0)
+class CatNode:                  # torch.cat of several tensors along channels (any channel counts)
     srcs: List[int]
     out: int
     kind: str = "cat"
@@ -106,7 +106,9 @@ def _groups(c_o: int) -> int:
 def unet_graph(levels, c_i, c_h, c_o, *, act, r_p, use_symm, repeats, f) -> NetGraph:
     """Layer wiring of Unet.__init__/forward (reference pytorch_networks_convae.py:1842-2024).  r_p = 'learned': every
     conv is a BoundaryLearnedConvolution2D node; the input is not padded — the first layer's bc_x = 4 strips grow the field
-    by the same 3 + 3 columns (:1990-1997) — and the two-operand concats are materialised (CatNode)."""
+    by the same 3 + 3 columns (:1990-1997) — and the two-operand concats are materialised (CatNode).  With fixed padding a
+    two-operand concat is the conv's two sources, unless its first operand does not fill whole channel blocks (c_h = 6, 12,
+    ...: the two-source conv kernels need c_in0 % 8 == 0); that concat is materialised too."""
     learned = r_p == "learned"
     ch: Dict[int, int] = {0: c_i}
     nodes = []
@@ -118,7 +120,7 @@ def unet_graph(levels, c_i, c_h, c_o, *, act, r_p, use_symm, repeats, f) -> NetG
         return nid[0]
 
     def one_src(srcs):
-        if not learned or len(srcs) == 1:
+        if len(srcs) == 1 or (not learned and all(ch[i] % 8 == 0 for i in srcs[:-1])):
             return list(srcs)
         cat = new(sum(ch[i] for i in srcs))
         nodes.append(CatNode(list(srcs), cat))
@@ -242,10 +244,12 @@ def _fluid_trunk(levels, c_i, c_h, *, act, r_p, use_symm, repeats, f, factor):
     :1642-1658): level l = the input feature map average-pooled l times, `repeats` FluidLayers, bicubic back to the input
     size; concat of the levels with the raw inputs.  The reference re-pools the feature map from scratch for every level; the
     values are identical to pooling the previous level once more, which is what the graph does.  Returns (channels, nodes,
-    tensor id of the concat, new-tensor function)."""
-    if c_h % 8:
-        raise NotImplementedError("the HIP path of NewFluidNet / FluidNet needs c_h to be a multiple of 8 (channel-block concat)")
+    tensor id of the concat, new-tensor function).  Any c_h with learned padding (the run list's configurations, pinned by
+    the reference goldens); with fixed padding c_h must stay a multiple of 8."""
     learned = r_p == "learned"
+    if c_h % 8 and not learned:
+        raise NotImplementedError("the HIP path of NewFluidNet / FluidNet with fixed padding needs c_h to be a multiple of 8 "
+                                  "(r_p='learned' takes any c_h)")
     ch: Dict[int, int] = {0: c_i}
     nodes = []
     nid = [0]
@@ -402,8 +406,8 @@ def shape_walk(g: NetGraph, N: int, H: int, W: int, precision: str):
             continue
         h, w = size[node.srcs[0]]
         if node.kind == "cat":
-            if any(size[t] != (h, w) for t in node.srcs) or any(g.channels[t] % 8 for t in node.srcs[:-1]):
-                raise ValueError("torch.cat operands must share H x W and all but the last need C % 8 == 0")
+            if any(size[t] != (h, w) for t in node.srcs):
+                raise ValueError("torch.cat operands must share H x W")
             size[node.out] = (h, w)
             grad[node.out] = True
             continue
@@ -592,7 +596,16 @@ class Engine:
             if node.kind == "cat":
                 o = T[node.out]
                 o.buf = cb8(o.C, o.H, o.W)
-                self.plan.append(dict(node=node))
+                # backward: an operand that is exactly its own channel blocks of the concat (starts on a block boundary, and
+                # is the last operand or fills whole blocks) reads its slice of the concat's gradient in place; any other
+                # gets a buffer of its own, gathered by mc_cat_grad_gather (offset: the operand's first channel)
+                gather, off = {}, 0
+                for k, t in enumerate(node.srcs):
+                    c = T[t].C
+                    if T[t].requires_grad and (off % 8 or (k < len(node.srcs) - 1 and c % 8)):
+                        gather[t] = (off, cb8g(c, o.H, o.W))
+                    off += c
+                self.plan.append(dict(node=node, gather=gather))
                 continue
             srcs = [T[t] for t in node.srcs]
             o = T[node.out]
@@ -920,7 +933,8 @@ class Engine:
         for e in reversed(self.plan):
             node = e["node"]
             if node.kind == "cat":
-                # the gradient of the concatenated tensor is one buffer; every operand reads its channel-block slice
+                # the gradient of the concatenated tensor is one buffer; an aligned operand reads its channel-block slice,
+                # an unaligned one its own buffer gathered from it (see configure)
                 o = T[node.out]
                 assert len(o.gsrcs) == 1, "a concatenated tensor feeds exactly one conv"
                 q = o.gsrcs[0]
@@ -928,9 +942,13 @@ class Engine:
                 off = 0
                 for i in node.srcs:
                     t = T[i]
-                    if t.requires_grad:
-                        t.gsrcs.append(L.GradSrc(q.ptr, q.kind, q.pad, q.pad_mode, q.pool, q.hs, q.ws, c8_total, off))
-                    off += (t.C + 7) // 8
+                    if i in e["gather"]:
+                        c_off, buf = e["gather"][i]
+                        L.call("mc_cat_grad_gather", C.byref(q), o.C, c_off, t.C, N, t.H, t.W, self.mc_gdtype, L.ptr(buf), st)
+                        t.gsrcs.append(L.GradSrc(L.ptr(buf), L.GSRC_PLAIN, 0, 0, 1, t.H, t.W))
+                    elif t.requires_grad:
+                        t.gsrcs.append(L.GradSrc(q.ptr, q.kind, q.pad, q.pad_mode, q.pool, q.hs, q.ws, c8_total, off // 8))
+                    off += t.C
                 continue
             if node.kind == "pool":
                 # d(src) += AvgPool adjoint of d(out); d(out) has one source (the conv it feeds) or two (+ the next pooling level)

@@ -798,10 +798,80 @@ def g22():
             out[f"count/{key}"] = np.array(P.count_parameters(m))
     npz("g22_fluidnet_modules", **out)
 
+def _unet6(r_p, seed):
+    """The run list's -f 6 Unet, small: 3 levels, c_h 6, two repeats, 5 x 5, curl head, p_pred off (network_lists.ipynb:
+    -net unet -l 5 -f 6 -p learned -s 0 -r 3 -k 5).  Its concats are [6, 6] and [6, 12]: no operand but the last fills
+    whole 8-channel blocks."""
+    m = P.Unet(3, 10, 6, 2, CPU, "gelu", r_p, "curl", use_symm=False, repeats=2, f=5, p_pred=False).double()
+    randomize_(m, seed)
+    with torch.no_grad():
+        g_ = torch.Generator().manual_seed(seed + 1)
+        for n, p in m.named_parameters():
+            if n.endswith("learnable_bias"):
+                p.copy_((0.1 * torch.randn(p.shape, generator=g_)).float().double())
+    return m
+
+
+def _grad_samples(m):
+    """Every parameter gradient, those of more than 512 entries as fields.strided_sample(g, 257) (the learned-padding banks would
+    otherwise double the file next to the state_dict)."""
+    return {"grad/" + k: (p.grad.float() if p.numel() <= 512 else fields.strided_sample(p.grad.float().numpy(), 257))
+            for k, p in m.named_parameters()}
+
+
+def g23():
+    # (a) the c_h = 6 Unet in learned and replicate padding: outputs, cotangents, state_dict and every parameter gradient
+    for tag, seed in (("learned", 230), ("replicate", 235)):
+        m = _unet6(tag, seed)
+        x = torch.from_numpy(fields.unet_input(2, 40, 54, seed + 2, c_i=10)).requires_grad_(True)
+        outs = m(x)
+        loss, save = 0.0, {}
+        for n, o in zip("uvpT", outs):
+            if o is None:
+                continue
+            ct = rnd(o.shape, seed + 3 + len(save))
+            loss = loss + (o * ct).sum()
+            save["out/" + n] = o
+            save["ct/" + n] = ct.float()
+        loss.backward()
+        save = {k_: v.detach().float() for k_, v in save.items()}
+        npz(f"g23_unet6_{tag}", cfg=np.array([3, 10, 6, 2, 2, 5, 0, 0]), r_p=np.array(tag), **save, **sd_np(m),
+            **_grad_samples(m))
+    # (b) NewFluidNet with c_h = 12 and learned padding: the trunk's concat is [12, 12, 7]
+    m = P.NewFluidNet(2, 7, 12, 1, CPU, "gelu", "learned", "curl", use_symm=False, repeats=1, f=5, p_pred=False).double()
+    randomize_(m, 238)
+    x = torch.from_numpy(fields.unet_input(1, 128, 506, 239, c_i=7)).requires_grad_(True)
+    outs = m(x)
+    loss, save = 0.0, {}
+    for n, o in zip("uvp", outs):
+        if o is None:
+            continue
+        # cotangents: fields.smooth_field(1, 128, 506, 240 + i) rounded to f32 (regenerated by the test, not stored)
+        ct = torch.from_numpy(fields.smooth_field(1, 128, 506, 240 + len(save)).astype(np.float32)).to(f64).view(o.shape)
+        loss = loss + (o * ct).sum()
+        save["out/" + n] = fields.strided_sample(o.detach().numpy(), 5003).astype(np.float32)
+    loss.backward()
+    npz("g23_newfluidnet12_learned", cfg=np.array([2, 7, 12, 1, 1, 5, 0, 0]), **save, **sd_np(m), **_grad_samples(m))
+    # (c) the reference's get_loss at roll_forward = 4 (4 x 4 chained evaluations) for the learned c_h = 6 Unet at its native
+    # 128 x 506 grid, loss_scale = loss_derivative = 1 (the run list's -l_sc 1 -l_de 1)
+    B, H, W, R = 1, 128, 506, 4
+    m = _unet6("learned", 230)
+    ns = _trainer_ns(m, False, True, True, "curl")
+    ns.roll_forward = R
+    gVTp = torch.from_numpy(fields.unet_input(B, H, W, 2330, c_i=10))
+    uvp = torch.from_numpy(np.stack([fields.smooth_field(B, H, W, 2331), fields.smooth_field(B, H, W, 2332),
+                                     fields.temperature_field(B, H, W, 2333)], 1))
+    paras = torch.tensor([[5.0, 1.0e7, 10.0]], dtype=f64).view(B, 3, 1, 1)
+    out = G.Trainer.get_loss(ns, gVTp, uvp, None, paras, gVTp[:, 1:2])
+    out[0].backward()
+    npz("g23_get_loss_unet6_roll4", losses=np.array([float(o) for o in out]), paras=paras.view(B, 3),
+        cfg=np.array([3, 10, 6, 2, 2, 5, 0, 0, 1, 1, R]), **_grad_samples(m))
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     torch.set_num_threads(8)
     only = sys.argv[1:]
-    for fn in (g1, g2, g3, g4, g5, g6, g7, g8, g9, g10, g11, g12, g13, g14, g15, g16, g17, g18, g19, g20, g21, g22):
+    for fn in (g1, g2, g3, g4, g5, g6, g7, g8, g9, g10, g11, g12, g13, g14, g15, g16, g17, g18, g19, g20, g21, g22, g23):
         if not only or fn.__name__ in only:
             fn()
