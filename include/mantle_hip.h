@@ -288,6 +288,54 @@ int mc_rect_copy(const void* src, int32_t hs, int32_t ws, int32_t sy, int32_t sx
                  int32_t dy, int32_t dx, int32_t rh, int32_t rw, int32_t n, int32_t c, int32_t accumulate, int32_t dtype,
                  void* stream);
 
+/* ---- learned padding: the FRAME of BoundaryLearnedConvolution2D (pytorch_networks_convae.py:1022-1065) --------------
+ * The layer is nine bias-free valid convolutions: the main bank on the whole input and eight border banks on the strips of
+ * width pad = k + 1 + (bc - 1) (k = 5) or k + (bc - 1) (k = 3), framed around the main result, plus one shared bias.  With
+ * f = pad - k + 1, mh = h - k + 1, mw = w - k + 1 the output is (mh + 2 fy) x (mw + 2 fx); the frame is every output pixel
+ * outside the mh x mw interior at (fy, fx).  The main bank runs on mc_conv2d / mc_conv2d_wgrad; the entry points below
+ * compute the frame of all eight border banks in ONE launch per direction, reading x / dy in place.
+ *   row class:    oy < fy: "bottom", window origin iy0 = h - pad_y + oy (the strip cut from the LAST input rows lands in the
+ *                 FIRST output rows, :1057-1060);  oy >= fy + mh: "top", iy0 = oy - (fy + mh);  else middle, iy0 = oy - fy
+ *   column class: ox < fx: "left", ix0 = ox;  ox >= fx + mw: "right", ix0 = w - pad_x + (ox - fx - mw);  else ix0 = ox - fx
+ * Bank arrays (w_unique, dw_unique) hold the eight border banks in the order
+ *   bottom_left, bottom, bottom_right, left, right, top_left, top, top_right
+ * each in the reference's layout [U][c_in][k][k] f32 (U = c_out - sym_h / 2 unique filters).
+ * dtype as everywhere: MC_MIX16 reads x / writes y as f16 and moves dy / dx as bf16. */
+typedef struct {
+  int32_t n;
+  int32_t h, w;        /* INPUT spatial size */
+  int32_t c_in, c_out; /* any counts; tail channels of a CB8 block are read as zero and stored as zero */
+  int32_t k;           /* 3 or 5 */
+  int32_t bc_x, bc_y;  /* >= 1: widen the strips by bc - 1 (the output grows) */
+  int32_t dtype;       /* MC_F32 | MC_BF16 | MC_MIX16 */
+  int32_t sym_h;       /* number of x-mirrored filters of every bank (even), 0 = plain Conv2d */
+} mc_learned_desc;
+
+/* Host-side check (needs no device): MC_OK, MC_EINVAL (NULL / non-positive sizes) or MC_EUNSUPPORTED for k not in {3, 5},
+ * h < pad_y, w < pad_x, h < k, w < k, an odd sym_h or an unknown dtype.  Every entry point below runs it first, so an input
+ * that is too small for the strips is refused before any launch. */
+int32_t mc_learned_validate(const mc_learned_desc* d);
+/* Bytes of the packed banks of all eight border banks (dgrad = 0: forward, 1: input gradient) and of the filter-gradient
+ * workspace; 0 for a descriptor mc_learned_validate refuses. */
+size_t mc_learned_bank_bytes(const mc_learned_desc* d, int32_t dgrad);
+size_t mc_learned_wgrad_workspace_bytes(const mc_learned_desc* d);
+/* Pack the border banks of n layers in batched launches: w_unique[8 * i + b] is bank b of layer i; fwd_banks[i] and
+ * dgrad_banks[i] (the array or an entry may be NULL: no input gradient) receive mc_learned_bank_bytes each. */
+int mc_learned_pack_banks_batched(const mc_learned_desc* descs, const float* const* w_unique, void* const* fwd_banks,
+                                  void* const* dgrad_banks, int32_t n, void* stream);
+/* y[frame] = bias + W_bank * x.  x: CB8 [n][c_in8][h][w]; y: CB8 [n][c_out8][ho][wo].  Elements of y outside the frame are
+ * not written. */
+int mc_learned_frame_fwd(const mc_learned_desc* d, const void* x, const void* fwd_bank, const float* bias, void* y,
+                         void* stream);
+/* dx += the eight border banks' input gradients (dx already holds the main bank's).  A gather over the input pixels of
+ * the border bands (rows < pad_y or >= h - pad_y, columns < pad_x or >= w - pad_x): each pixel is owned by one thread that
+ * sums every bank's contribution, so the result does not depend on block order; pixels outside the bands are not written. */
+int mc_learned_frame_dgrad(const mc_learned_desc* d, const void* dy, const void* dgrad_bank, void* dx, void* stream);
+/* dw_unique[b] += filter gradient of border bank b (mirrored filters folded back), dbias += the sum of dy over the frame.
+ * Two launches: per-slice partial slabs into `workspace`, then a reduce in fixed order (bit-reproducible). */
+int mc_learned_frame_wgrad(const mc_learned_desc* d, const void* x, const void* dy, void* workspace,
+                           float* const* dw_unique, float* dbias, void* stream);
+
 /* ---- resampling (nn.AvgPool2d, nn.Upsample(mode='bicubic'); Unet :2002,2009,2014; ConvAE :1051,1079) */
 int mc_avgpool_fwd(const void* x, int32_t n, int32_t c, int32_t h, int32_t w, int32_t f, int32_t dtype,
                    void* out, void* stream);

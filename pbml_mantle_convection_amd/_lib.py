@@ -24,6 +24,16 @@ class ConvDesc(C.Structure):
                                           "dtype", "sym_h", "c_out_split", "out_f32", "sym_v", "sym_hv")]
 
 
+class LearnedDesc(C.Structure):
+    """mc_learned_desc: the frame (eight border banks) of a BoundaryLearnedConvolution2D layer."""
+    _fields_ = [(n, C.c_int32) for n in ("n", "h", "w", "c_in", "c_out", "k", "bc_x", "bc_y", "dtype", "sym_h")]
+
+
+# order of the eight border banks in the bank arrays of the mc_learned_* entry points
+LEARNED_FRAME_BANKS = ("conv_bottom_left", "conv_bottom", "conv_bottom_right", "conv_left", "conv_right", "conv_top_left",
+                       "conv_top", "conv_top_right")
+
+
 class GradSrc(C.Structure):
     _fields_ = [("ptr", C.c_void_p), ("kind", C.c_int32), ("pad", C.c_int32), ("pad_mode", C.c_int32),
                 ("pool", C.c_int32), ("hs", C.c_int32), ("ws", C.c_int32), ("c8_total", C.c_int32), ("cb_off", C.c_int32)]
@@ -51,6 +61,7 @@ class LossDesc(C.Structure):
 _vp, _i32, _i64, _f32, _sz = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_size_t
 _CD, _GS, _LD = C.POINTER(ConvDesc), C.POINTER(GradSrc), C.POINTER(LossDesc)
 _CP, _CE = C.POINTER(ConvPrologue), C.POINTER(ConvEpilogue)
+_LN = C.POINTER(LearnedDesc)
 
 # name -> (restype, argtypes); must list EVERY symbol include/mantle_hip.h declares
 SIGNATURES = {
@@ -99,6 +110,13 @@ SIGNATURES = {
     "mc_avgpool_fwd": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "mc_rect_copy": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
                                _vp]),
+    "mc_learned_validate": (_i32, [_LN]),
+    "mc_learned_bank_bytes": (_sz, [_LN, _i32]),
+    "mc_learned_wgrad_workspace_bytes": (_sz, [_LN]),
+    "mc_learned_pack_banks_batched": (C.c_int, [_LN, _vp, _vp, _vp, _i32, _vp]),
+    "mc_learned_frame_fwd": (C.c_int, [_LN, _vp, _vp, _vp, _vp, _vp]),
+    "mc_learned_frame_dgrad": (C.c_int, [_LN, _vp, _vp, _vp, _vp]),
+    "mc_learned_frame_wgrad": (C.c_int, [_LN, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mc_concat_cb8": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "mc_gsrc_sum": (C.c_int, [_GS, _GS, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "mc_cat_grad_gather": (C.c_int, [_GS, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
@@ -138,7 +156,8 @@ SIGNATURES = {
 
 # entry points whose return value is a quantity, not a status code
 VALUE_RETURNING = {"mc_version", "mc_strerror", "mc_conv_kernel_name", "mc_packed_weight_bytes", "mc_conv_bank_read_extent", "mc_conv_tiles",
-                   "mc_wgrad_partial_bytes", "mc_gn_bwd_blocks", "mc_fold_blocks", "mc_loss_fused_blocks"}
+                   "mc_wgrad_partial_bytes", "mc_gn_bwd_blocks",
+                   "mc_learned_validate", "mc_learned_bank_bytes", "mc_learned_wgrad_workspace_bytes", "mc_fold_blocks", "mc_loss_fused_blocks"}
 
 _lib = None
 

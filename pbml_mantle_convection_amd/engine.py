@@ -92,6 +92,7 @@ class NetGraph:
     pad_mode: str = "zeros"
     act: str = "gelu"
     divisor: int = 1           # H, W must be divisible by this (ConvAE: 4**levels)
+    input_grad: bool = False   # backward also produces the gradient w.r.t. the network input (single-layer graphs, tests)
 
 
 def _sym_h(c_o: int) -> int:
@@ -335,12 +336,15 @@ def fluidnet_graph(levels, c_i, c_h, c_o, *, act, r_p, use_symm, repeats, f, fac
 
 
 def single_layer_graph(c_in, c_out, k, pad, pad_mode, sym_h, post, act, groups, gn: bool, learned: bool = False,
-                       sym_v: int = 0, sym_hv: int = 0) -> NetGraph:
-    """One conv (+GN+act): SymmetricConv2d / FluidLayer used stand-alone."""
+                       sym_v: int = 0, sym_hv: int = 0, bc_x: int = 1, bc_y: int = 1, input_grad: bool = False) -> NetGraph:
+    """One conv (+GN+act): SymmetricConv2d / FluidLayer / BoundaryLearnedConvolution2D (learned; bc_x, bc_y as in its forward)
+    used stand-alone.  input_grad (learned layers): backward leaves d(loss)/d(input) in Engine.input_grad_cb8()."""
+    if input_grad and not learned:
+        raise NotImplementedError("input_grad is implemented for learned-padding layers")
     ch = {0: c_in, 1: c_out}
     node = ConvNode("layers.0." if gn else "", [0], 1, c_out, k, pad, sym_h, post, "layers.1." if gn else None, groups,
-                    learned=learned, sym_v=sym_v, sym_hv=sym_hv)
-    return NetGraph(c_in, c_out, ch, [node], pad_mode=pad_mode, act=act)
+                    learned=learned, sym_v=sym_v, sym_hv=sym_hv, bc_x=bc_x, bc_y=bc_y)
+    return NetGraph(c_in, c_out, ch, [node], pad_mode=pad_mode, act=act, input_grad=input_grad)
 
 
 # learned padding (BoundaryLearnedConvolution2D): parameter order of the nine banks (the reference's sub-modules)
@@ -351,7 +355,8 @@ BANKS = ("conv", "conv_top_left", "conv_top_right", "conv_bottom_left", "conv_bo
 def learned_regions(h, w, k, bc_x=1, bc_y=1):
     """Geometry of the nine banks on an h x w input: (fy, fx, ho, wo, {bank: (sy, sx, sh, sw, dy, dx)}) -- the frame widths,
     the output size and, per bank, the input rectangle it convolves (valid) and where its result lands in the output.  The
-    strips are k + 1 (k = 5) or k wide, bc > 1 widens them by bc - 1.  Banks come in launch order: the main bank first."""
+    strips are k + 1 (k = 5) or k wide, bc > 1 widens them by bc - 1.  The main bank comes first (the engine launches it on
+    the conv kernels; the other eight are the frame of mc_learned_frame_*)."""
     pad_x = k + 1 + (bc_x - 1) if k == 5 else k + (bc_x - 1)
     pad_y = k + 1 + (bc_y - 1) if k == 5 else k + (bc_y - 1)
     fx, fy, mh, mw = pad_x - k + 1, pad_y - k + 1, h - k + 1, w - k + 1
@@ -371,7 +376,7 @@ class ConvShape:
     d: Optional[L.ConvDesc] = None       # forward
     dd: Optional[L.ConvDesc] = None      # input gradient (None when no source needs one)
     final_f32: bool = False              # the head writes its output in f32
-    banks: Optional[dict] = None         # learned padding: bank -> (region, d, dd) in launch order; d / dd stay None
+    banks: Optional[dict] = None         # learned padding: bank -> (region, d, dd), the main bank first; d / dd stay None
 
 
 def _conv_descs(N, h, w, cs, c_out, k, pad, mode, mc, mcg, sym=(0, 0, 0), out_f32=False, dgrad=True):
@@ -393,7 +398,7 @@ def shape_walk(g: NetGraph, N: int, H: int, W: int, precision: str):
     mcg = L.MC_BF16 if mc == L.MC_MIX16 else mc
     mode = L.PAD_MODES[g.pad_mode]
     size = {0: (H, W + 2 * g.in_pad_w)}
-    grad = {0: False}
+    grad = {0: g.input_grad}
     convs: Dict[int, ConvShape] = {}
     for i, node in enumerate(g.nodes):
         if node.kind == "up":
@@ -688,6 +693,9 @@ class Engine:
         # launches have read it before the next layer down writes its own
         self.dY = torch.empty(max_dy, dtype=self.g_dtype, device=device)
         self.convs = [e for e in self.plan if e["node"].kind == "conv" and not e["node"].learned]
+        self.learned = [e for e in self.plan if e["node"].kind == "conv" and e["node"].learned]
+        # one filter-gradient workspace for the frames of every learned layer (backward is one stream)
+        self.lws = torch.empty(max([e["lws_bytes"] for e in self.learned] + [0]), dtype=torch.uint8, device=device)
         last = self.plan[-1]
         assert last["node"].kind == "conv", "graph must end in a conv node"
         self.final_plain = last["node"].post == L.POST_NONE
@@ -701,25 +709,36 @@ class Engine:
 
     # -------------------------------------------------------------- learned padding (BoundaryLearnedConvolution2D)
     def _plan_learned(self, node, shape, s, o, cb8, cb8g, f32):
-        """Nine bias-free valid convolutions on the library's conv kernels, the strips cut / the frame assembled with
-        mc_rect_copy (reference pytorch_networks_convae.py:1022-1065).  The gradient w.r.t. the input needs no padded
-        domain: the adjoint of a valid convolution is exactly input-sized."""
+        """The main bank on the library's conv kernels, the frame of the eight border banks on the mc_learned_frame_* kernels,
+        which read the input / the output gradient in place (reference pytorch_networks_convae.py:1022-1065).  The gradient
+        w.r.t. the input needs no padded domain: the adjoint of a valid convolution is exactly input-sized."""
         N, u8 = self.N, dict(dtype=torch.uint8, device=self.device)
-        banks = {}
-        for name, (reg, d, dd) in shape.banks.items():
-            if L.call("mc_conv_tiles", C.byref(d)) <= 0:
-                raise L.MantleHipError(f"unsupported convolution configuration for {node.name}{name}")
-            sh, sw, rh, rw = reg[2], reg[3], dd.h, dd.w           # (dd.h x dd.w: the valid convolution's output)
-            banks[name] = dict(desc=d, ddesc=dd, reg=reg, rh=rh, rw=rw,
-                               S=None if name == "conv" else cb8(s.C, sh, sw), R=cb8(node.c_out, rh, rw),
-                               dR=cb8g(node.c_out, rh, rw), dS=cb8g(s.C, sh, sw),
-                               bank=torch.empty(L.call("mc_packed_weight_bytes", C.byref(d), 0), **u8),
-                               dbank=torch.empty(L.call("mc_packed_weight_bytes", C.byref(d), 1), **u8),
-                               wpart=torch.empty(L.call("mc_wgrad_partial_bytes", C.byref(d)), **u8))
+        reg, d, dd = shape.banks["conv"]                          # the valid convolution on the whole input
+        ld = L.LearnedDesc(N, s.H, s.W, s.C, node.c_out, node.k, node.bc_x, node.bc_y, self.mc_dtype, node.sym_h)
+        if L.call("mc_learned_validate", C.byref(ld)) != 0 or L.call("mc_conv_tiles", C.byref(d)) <= 0:
+            raise L.MantleHipError(f"unsupported learned-padding configuration for {node.name} ({self.precision}, "
+                                   f"c_in={s.C}, c_out={node.c_out}, k={node.k}, input {s.H}x{s.W})")
+        fy, fx, mh, mw = reg[4], reg[5], dd.h, dd.w
+        # square frame: the main bank as a zero-padded convolution straight into Y -- its interior is the valid result, its
+        # frame is overwritten by the frame launch; otherwise the valid result is placed with one mc_rect_copy
+        fd = d
+        if fx == fy and fx <= node.k - 1:
+            fd = L.ConvDesc(N, s.H, s.W, s.C, 0, node.c_out, node.k, fx, L.PAD_MODES["zeros"], self.mc_dtype, node.sym_h, 0, 0)
+            if L.call("mc_conv_tiles", C.byref(fd)) <= 0:
+                fd = d
         coutp = ((node.c_out + 7) // 8) * 8
         tiles = min(64, o.H)
-        e = dict(node=node, banks=banks, tiles=tiles, coutp=coutp, Y=cb8(node.c_out, o.H, o.W),
-                 part=torch.empty((N, tiles, coutp, 2), **f32), need_dgrad=s.requires_grad, dxl=cb8g(s.C, s.H, s.W), desc=None)
+        need_dgrad = s.requires_grad
+        e = dict(node=node, ldesc=ld, desc=d, fdesc=fd, ddesc=dd, fy=fy, fx=fx, mh=mh, mw=mw, tiles=tiles, coutp=coutp,
+                 Y=cb8(node.c_out, o.H, o.W), R=None if fd is not d else cb8(node.c_out, mh, mw), dR=cb8g(node.c_out, mh, mw),
+                 part=torch.empty((N, tiles, coutp, 2), **f32), need_dgrad=need_dgrad,
+                 dxl=cb8g(s.C, s.H, s.W) if need_dgrad else None,
+                 bank=torch.empty(L.call("mc_packed_weight_bytes", C.byref(fd), 0), **u8),
+                 dbank=torch.empty(L.call("mc_packed_weight_bytes", C.byref(d), 1), **u8) if need_dgrad else None,
+                 wpart=torch.empty(L.call("mc_wgrad_partial_bytes", C.byref(d)), **u8),
+                 lbank=torch.empty(L.call("mc_learned_bank_bytes", C.byref(ld), 0), **u8),
+                 ldbank=torch.empty(L.call("mc_learned_bank_bytes", C.byref(ld), 1), **u8) if need_dgrad else None,
+                 lws_bytes=L.call("mc_learned_wgrad_workspace_bytes", C.byref(ld)))
         o.buf = cb8(node.c_out, o.H, o.W) if node.post != L.POST_NONE else e["Y"]
         if node.post == L.POST_GN_ACT:
             e["stats"] = torch.empty((N, node.groups, 2), **f32)
@@ -732,43 +751,38 @@ class Engine:
         node, N = e["node"], self.N
         bias = self._param(params, node.name + "learnable_bias")
         o_h, o_w = e["Y"].shape[2], e["Y"].shape[3]
-        for name, b in e["banks"].items():
-            sy, sx, sh, sw, dy, dx = b["reg"]
-            w = self._param(params, node.name + name + ".weight")
-            xin = src.buf
-            if b["S"] is not None:
-                L.call("mc_rect_copy", L.ptr(src.buf), src.H, src.W, sy, sx, L.ptr(b["S"]), sh, sw, 0, 0, sh, sw, N, src.C, 0,
-                       self.mc_dtype, st)
-                xin = b["S"]
-            L.call("mc_pack_weights", C.byref(b["desc"]), L.ptr(w), 0, L.ptr(b["bank"]), st)
-            L.call("mc_conv2d", C.byref(b["desc"]), L.ptr(xin), None, L.ptr(b["bank"]), L.ptr(bias), L.ptr(b["R"]), None, None, st)
-            L.call("mc_rect_copy", L.ptr(b["R"]), b["rh"], b["rw"], 0, 0, L.ptr(e["Y"]), o_h, o_w, dy, dx, b["rh"], b["rw"], N,
-                   node.c_out, 0, self.mc_dtype, st)
+        main = e["Y"] if e["R"] is None else e["R"]
+        L.call("mc_conv2d", C.byref(e["fdesc"]), L.ptr(src.buf), None, L.ptr(e["bank"]), L.ptr(bias), L.ptr(main), None, None, st)
+        if e["R"] is not None:
+            L.call("mc_rect_copy", L.ptr(e["R"]), e["mh"], e["mw"], 0, 0, L.ptr(e["Y"]), o_h, o_w, e["fy"], e["fx"], e["mh"], e["mw"],
+                   N, node.c_out, 0, self.mc_dtype, st)
+        L.call("mc_learned_frame_fwd", C.byref(e["ldesc"]), L.ptr(src.buf), L.ptr(e["lbank"]), L.ptr(bias), L.ptr(e["Y"]), st)
         if need_part:
             L.call("mc_gn_partials", L.ptr(e["Y"]), N, node.c_out, o_h, o_w, self.mc_dtype, e["tiles"], L.ptr(e["part"]), st)
 
     def _learned_backward(self, e, src, dY, params, grads, st):
+        """The main bank's filter gradient joins the batched combine at the end of backward (e["wpart"]); its input gradient
+        initialises dxl, the frame launch adds the eight border banks' to the border bands of dxl."""
         node, N = e["node"], self.N
         o_h, o_w = e["Y"].shape[2], e["Y"].shape[3]
-        db = grads[node.name + "learnable_bias"]
-        for name, b in e["banks"].items():                      # "conv" comes first: its input gradient initialises dxl
-            sy, sx, sh, sw, dy, dx = b["reg"]
-            L.call("mc_rect_copy", L.ptr(dY), o_h, o_w, dy, dx, L.ptr(b["dR"]), b["rh"], b["rw"], 0, 0, b["rh"], b["rw"], N, node.c_out,
-                   0, self.mc_gdtype, st)
-            xin = src.buf if b["S"] is None else b["S"]
-            L.call("mc_conv2d_wgrad", C.byref(b["desc"]), L.ptr(xin), None, L.ptr(b["dR"]), L.ptr(b["wpart"]), st)
-            L.call("mc_conv2d_wgrad_finalize", C.byref(b["desc"]), L.ptr(b["wpart"]), L.ptr(grads[node.name + name + ".weight"]),
-                   L.ptr(db), st)
-            if e["need_dgrad"]:
-                w = self._param(params, node.name + name + ".weight")
-                L.call("mc_pack_weights", C.byref(b["desc"]), L.ptr(w), 1, L.ptr(b["dbank"]), st)
-                tgt = e["dxl"] if name == "conv" else b["dS"]
-                L.call("mc_conv2d", C.byref(b["ddesc"]), L.ptr(b["dR"]), None, L.ptr(b["dbank"]), None, L.ptr(tgt), None, None, st)
-                if name != "conv":
-                    L.call("mc_rect_copy", L.ptr(b["dS"]), sh, sw, 0, 0, L.ptr(e["dxl"]), src.H, src.W, sy, sx, sh, sw, N, src.C, 1,
-                           self.mc_gdtype, st)
+        L.call("mc_rect_copy", L.ptr(dY), o_h, o_w, e["fy"], e["fx"], L.ptr(e["dR"]), e["mh"], e["mw"], 0, 0, e["mh"], e["mw"], N,
+               node.c_out, 0, self.mc_gdtype, st)
+        L.call("mc_conv2d_wgrad", C.byref(e["desc"]), L.ptr(src.buf), None, L.ptr(e["dR"]), L.ptr(e["wpart"]), st)
+        dws = (C.c_void_p * 8)(*[L.ptr(grads[node.name + b + ".weight"]) for b in L.LEARNED_FRAME_BANKS])
+        L.call("mc_learned_frame_wgrad", C.byref(e["ldesc"]), L.ptr(src.buf), L.ptr(dY), L.ptr(self.lws), dws,
+               L.ptr(grads[node.name + "learnable_bias"]), st)
         if e["need_dgrad"]:
+            L.call("mc_conv2d", C.byref(e["ddesc"]), L.ptr(e["dR"]), None, L.ptr(e["dbank"]), None, L.ptr(e["dxl"]), None, None, st)
+            L.call("mc_learned_frame_dgrad", C.byref(e["ldesc"]), L.ptr(dY), L.ptr(e["ldbank"]), L.ptr(e["dxl"]), st)
             src.gsrcs.append(L.GradSrc(L.ptr(e["dxl"]), L.GSRC_PLAIN, 0, 0, 1, src.H, src.W))
+
+    def input_grad_cb8(self):
+        """d(loss)/d(input) of a graph built with input_grad=True, as backward left it: CB8 [N][C8][H][W][8] in the gradient
+        type (the first node must be a learned-padding layer reading the input)."""
+        e = self.plan[0]
+        if not self.g.input_grad or not e["node"].kind == "conv" or e.get("dxl") is None:
+            raise RuntimeError("this graph produces no input gradient")
+        return e["dxl"]
 
     def _table(self, n_in, n_out):
         key = (n_in, n_out)
@@ -1074,31 +1088,46 @@ class Engine:
                    (C.c_int32 * n)(*[j[1] for j in gp_jobs]), (C.c_void_p * n)(*[j[2] for j in gp_jobs]),
                    (C.c_void_p * n)(*[j[3] for j in gp_jobs]), n, st)
         # one launch combines every layer's partial slabs, folds mirrored filters and accumulates into the gradients
-        n = len(self.convs)
+        # (a learned layer's main bank: its valid convolution; the shared bias takes its interior share here)
+        jobs = [(e["desc"], e["wpart"], e["node"].name + "weight", e["node"].name + "bias") for e in self.convs]
+        jobs += [(e["desc"], e["wpart"], e["node"].name + "conv.weight", e["node"].name + "learnable_bias") for e in self.learned]
+        n = len(jobs)
         if n:
-            descs = (L.ConvDesc * n)(*[e["desc"] for e in self.convs])
-            parts = (C.c_void_p * n)(*[L.ptr(e["wpart"]) for e in self.convs])
-            dws = (C.c_void_p * n)(*[L.ptr(grads[e["node"].name + "weight"]) for e in self.convs])
-            dbs = (C.c_void_p * n)(*[L.ptr(grads[e["node"].name + "bias"]) for e in self.convs])
+            descs = (L.ConvDesc * n)(*[j[0] for j in jobs])
+            parts = (C.c_void_p * n)(*[L.ptr(j[1]) for j in jobs])
+            dws = (C.c_void_p * n)(*[L.ptr(grads[j[2]]) for j in jobs])
+            dbs = (C.c_void_p * n)(*[L.ptr(grads[j[3]]) for j in jobs])
             L.call("mc_conv2d_wgrad_finalize_batched", descs, parts, dws, dbs, n, st)
 
     def _pack_all_banks(self, params, st):
         """Forward and input-gradient banks of every layer in one batched launch per 24 jobs (weights are fixed
-        within a step)."""
+        within a step); the eight border banks of every learned-padding layer in one launch per 16 layers."""
         jobs = []
         for e in self.convs:
             w = self._param(params, e["node"].name + "weight")
             jobs.append((e["desc"], L.ptr(w), 0, L.ptr(e["bank"])))
             if e["need_dgrad"]:
                 jobs.append((e["desc"], L.ptr(w), 1, L.ptr(e["dbank"])))
+        for e in self.learned:                               # main banks: forward as launched (fdesc), gradient of the valid conv
+            w = self._param(params, e["node"].name + "conv.weight")
+            jobs.append((e["fdesc"], L.ptr(w), 0, L.ptr(e["bank"])))
+            if e["need_dgrad"]:
+                jobs.append((e["desc"], L.ptr(w), 1, L.ptr(e["dbank"])))
         n = len(jobs)
-        if n == 0:
-            return                                           # (a graph of learned-padding layers only)
-        descs = (L.ConvDesc * n)(*[j[0] for j in jobs])
-        ws = (C.c_void_p * n)(*[j[1] for j in jobs])
-        dg = (C.c_int32 * n)(*[j[2] for j in jobs])
-        outs = (C.c_void_p * n)(*[j[3] for j in jobs])
-        L.call("mc_pack_weights_batched", descs, ws, dg, outs, n, st)
+        if n:
+            descs = (L.ConvDesc * n)(*[j[0] for j in jobs])
+            ws = (C.c_void_p * n)(*[j[1] for j in jobs])
+            dg = (C.c_int32 * n)(*[j[2] for j in jobs])
+            outs = (C.c_void_p * n)(*[j[3] for j in jobs])
+            L.call("mc_pack_weights_batched", descs, ws, dg, outs, n, st)
+        n = len(self.learned)
+        if n:
+            descs = (L.LearnedDesc * n)(*[e["ldesc"] for e in self.learned])
+            ws = (C.c_void_p * (8 * n))(*[L.ptr(self._param(params, e["node"].name + b + ".weight"))
+                                          for e in self.learned for b in L.LEARNED_FRAME_BANKS])
+            fw = (C.c_void_p * n)(*[L.ptr(e["lbank"]) for e in self.learned])
+            dg = (C.c_void_p * n)(*[L.ptr(e["ldbank"]) for e in self.learned])
+            L.call("mc_learned_pack_banks_batched", descs, ws, fw, dg, n, st)
 
     # -------------------------------------------------------------- measurement hooks (bench.py)
     _probe = None

@@ -2,11 +2,11 @@
 §8(f) row N4) on the HIP path: nine bias-free VALID convolutions (one on the whole input, eight on the border strips of
 width k + 1 / k) framed together, plus one shared bias.
 
-Every convolution, its filter gradient and its input gradient run on the library's conv kernels (`mc_conv2d`,
-`mc_conv2d_wgrad*`); the strips are cut and the frame is assembled with `mc_rect_copy`.  The main bank runs as a
-zero-padded 'same' convolution straight into the output (its interior is the valid result), the eight strip results then
-overwrite the frame.  As in the reference, the strip cut from the LAST rows lands in the FIRST output rows and vice versa
-(:1057-1060).  Only bc_x = bc_y = 1 (output size = input size) is implemented.
+The main bank runs on the library's conv kernels (`mc_conv2d`, `mc_conv2d_wgrad*`) as a zero-padded 'same' convolution
+straight into the output (its interior is the valid result); the frame of the eight border banks -- forward, filter
+gradient and input gradient -- is one `mc_learned_frame_*` launch per direction that reads the input / the output
+gradient in place.  As in the reference, the strip cut from the LAST rows lands in the FIRST output rows and vice versa
+(:1057-1060).  Only bc_x = bc_y = 1 (output size = input size) is implemented here; the engine's learned node takes any bc.
 """
 from __future__ import annotations
 
@@ -28,37 +28,31 @@ class _Plan:
         self.key = (N, H, W, precision, str(device))
         self.N, self.H, self.W, self.c_i, self.c_o, self.k = N, H, W, c_i, c_o, k
         self.mc, self.td = _DT[precision]
-        self.f, _, _, _, regions = learned_regions(H, W, k)          # (fy = fx for bc = 1)
-        self.regions = {n: r for n, r in regions.items() if n != "conv"}
-        if H < 2 * self.f + 1 + (k - 1) or W < 2 * self.f + 1 + (k - 1):
+        self.f = learned_regions(H, W, k)[0]                         # (fy = fx for bc = 1)
+        self.ld = L.LearnedDesc(N, H, W, c_i, c_o, k, 1, 1, self.mc, sym_h)
+        if L.call("mc_learned_validate", C.byref(self.ld)) != 0:
             raise ValueError("input too small for the learned-padding strips")
-        dev = device
+        dev, u8 = device, dict(dtype=torch.uint8, device=device)
 
         def cb8(c, h, w):
             return torch.empty((N, (c + 7) // 8, h, w, 8), dtype=self.td, device=dev)
 
-        def conv_entry(h, w, pad):
-            d = L.ConvDesc(N, h, w, c_i, 0, c_o, k, pad, L.PAD_MODES["zeros"], self.mc, sym_h, 0, 0)
-            ho, wo = h + 2 * pad - k + 1, w + 2 * pad - k + 1
-            dd = L.ConvDesc(N, ho, wo, c_o, 0, c_i, k, k - 1, 0, self.mc, 0, 0, 0)
-            if L.call("mc_conv_tiles", C.byref(d)) <= 0:
-                raise L.MantleHipError("unsupported convolution configuration in BoundaryLearnedConvolution2D")
-            return dict(desc=d, ddesc=dd, ho=ho, wo=wo,
-                        bank=torch.empty(L.call("mc_packed_weight_bytes", C.byref(d), 0), dtype=torch.uint8, device=dev),
-                        dbank=torch.empty(L.call("mc_packed_weight_bytes", C.byref(d), 1), dtype=torch.uint8, device=dev),
-                        wpart=torch.empty(L.call("mc_wgrad_partial_bytes", C.byref(d)), dtype=torch.uint8, device=dev))
-
+        self.mh, self.mw = H - k + 1, W - k + 1
+        # forward: 'same' convolution with zero padding f; gradients: the valid convolution (output mh x mw) and its adjoint
+        self.fdesc = L.ConvDesc(N, H, W, c_i, 0, c_o, k, self.f, L.PAD_MODES["zeros"], self.mc, sym_h, 0, 0)
+        self.desc = L.ConvDesc(N, H, W, c_i, 0, c_o, k, 0, L.PAD_MODES["zeros"], self.mc, sym_h, 0, 0)
+        self.ddesc = L.ConvDesc(N, self.mh, self.mw, c_o, 0, c_i, k, k - 1, 0, self.mc, 0, 0, 0)
+        if min(L.call("mc_conv_tiles", C.byref(d)) for d in (self.fdesc, self.desc, self.ddesc)) <= 0:
+            raise L.MantleHipError("unsupported convolution configuration in BoundaryLearnedConvolution2D")
+        self.bank = torch.empty(L.call("mc_packed_weight_bytes", C.byref(self.fdesc), 0), **u8)
+        self.dbank = torch.empty(L.call("mc_packed_weight_bytes", C.byref(self.desc), 1), **u8)
+        self.wpart = torch.empty(L.call("mc_wgrad_partial_bytes", C.byref(self.desc)), **u8)
+        self.lbank = torch.empty(L.call("mc_learned_bank_bytes", C.byref(self.ld), 0), **u8)
+        self.ldbank = torch.empty(L.call("mc_learned_bank_bytes", C.byref(self.ld), 1), **u8)
+        self.lws = torch.empty(L.call("mc_learned_wgrad_workspace_bytes", C.byref(self.ld)), **u8)
         self.X, self.Y = cb8(c_i, H, W), cb8(c_o, H, W)
-        self.dY, self.dYm = cb8(c_o, H, W), cb8(c_o, H, W)
-        self.main = conv_entry(H, W, self.f)
-        self.dXP = cb8(c_i, H + 2 * self.f, W + 2 * self.f)
+        self.dY, self.dR = cb8(c_o, H, W), cb8(c_o, self.mh, self.mw)
         self.dX = cb8(c_i, H, W)
-        self.strips = {}
-        for name, (sy, sx, sh, sw, dy, dx) in self.regions.items():
-            e = conv_entry(sh, sw, 0)
-            e.update(S=cb8(c_i, sh, sw), R=cb8(c_o, e["ho"], e["wo"]), dR=cb8(c_o, e["ho"], e["wo"]), dS=cb8(c_i, sh, sw),
-                     reg=(sy, sx, sh, sw, dy, dx))
-            self.strips[name] = e
 
 
 class _LearnedConvFn(torch.autograd.Function):
@@ -72,16 +66,13 @@ class _LearnedConvFn(torch.autograd.Function):
         ws = {n: w.detach().float().contiguous() for n, w in zip(BANKS, weights)}
         b = bias.detach().float().reshape(-1).contiguous()
         L.call("mc_pack_nchw", L.ptr(x), N, p.c_i, Ci, H, W, 0, 0, None, p.mc, L.ptr(p.X), st)
-        m = p.main
-        L.call("mc_pack_weights", C.byref(m["desc"]), L.ptr(ws["conv"]), 0, L.ptr(m["bank"]), st)
-        L.call("mc_conv2d", C.byref(m["desc"]), L.ptr(p.X), None, L.ptr(m["bank"]), L.ptr(b), L.ptr(p.Y), None, None, st)
-        for name, e in p.strips.items():
-            sy, sx, sh, sw, dy, dx = e["reg"]
-            L.call("mc_rect_copy", L.ptr(p.X), H, W, sy, sx, L.ptr(e["S"]), sh, sw, 0, 0, sh, sw, N, p.c_i, 0, p.mc, st)
-            L.call("mc_pack_weights", C.byref(e["desc"]), L.ptr(ws[name]), 0, L.ptr(e["bank"]), st)
-            L.call("mc_conv2d", C.byref(e["desc"]), L.ptr(e["S"]), None, L.ptr(e["bank"]), L.ptr(b), L.ptr(e["R"]), None, None, st)
-            L.call("mc_rect_copy", L.ptr(e["R"]), e["ho"], e["wo"], 0, 0, L.ptr(p.Y), H, W, dy, dx, e["ho"], e["wo"], N, p.c_o, 0,
-                   p.mc, st)
+        # the main bank's forward and input-gradient banks in one launch, the eight border banks (both directions) in another
+        L.call("mc_pack_weights_batched", (L.ConvDesc * 2)(p.fdesc, p.desc), (C.c_void_p * 2)(L.ptr(ws["conv"]), L.ptr(ws["conv"])),
+               (C.c_int32 * 2)(0, 1), (C.c_void_p * 2)(L.ptr(p.bank), L.ptr(p.dbank)), 2, st)
+        L.call("mc_learned_pack_banks_batched", C.byref(p.ld), (C.c_void_p * 8)(*[L.ptr(ws[n]) for n in L.LEARNED_FRAME_BANKS]),
+               (C.c_void_p * 1)(L.ptr(p.lbank)), (C.c_void_p * 1)(L.ptr(p.ldbank)), 1, st)
+        L.call("mc_conv2d", C.byref(p.fdesc), L.ptr(p.X), None, L.ptr(p.bank), L.ptr(b), L.ptr(p.Y), None, None, st)
+        L.call("mc_learned_frame_fwd", C.byref(p.ld), L.ptr(p.X), L.ptr(p.lbank), L.ptr(b), L.ptr(p.Y), st)
         out = torch.empty((N, p.c_o, H, W), dtype=torch.float32, device=x.device)
         L.call("mc_unpack_nchw", L.ptr(p.Y), N, p.c_o, H, W, 0, None, p.mc, L.ptr(out), st)
         mod._version += 1
@@ -100,28 +91,16 @@ class _LearnedConvFn(torch.autograd.Function):
         gout = gout.float().contiguous()
         dev = gout.device
         L.call("mc_pack_nchw", L.ptr(gout), N, p.c_o, p.c_o, H, W, 0, 0, None, p.mc, L.ptr(p.dY), st)
-        # the main bank only sees the interior of dY: its frame belongs to the eight strip banks
-        L.call("mc_rect_copy", L.ptr(p.dY), H, W, 0, 0, L.ptr(p.dYm), H, W, 0, 0, H, W, N, p.c_o, 0, p.mc, st)
-        for (zy, zx, zh, zw) in ((0, 0, f, W), (H - f, 0, f, W), (0, 0, H, f), (0, W - f, H, f)):
-            L.call("mc_rect_copy", None, 0, 0, 0, 0, L.ptr(p.dYm), H, W, zy, zx, zh, zw, N, p.c_o, 0, p.mc, st)
+        # the main bank only sees the interior of dY: its frame belongs to the eight border banks
+        L.call("mc_rect_copy", L.ptr(p.dY), H, W, f, f, L.ptr(p.dR), p.mh, p.mw, 0, 0, p.mh, p.mw, N, p.c_o, 0, p.mc, st)
         dws = {n: torch.zeros_like(ws[n]) for n in BANKS}
         db = torch.zeros(p.c_o, dtype=torch.float32, device=dev)
-        m = p.main
-        L.call("mc_conv2d_wgrad", C.byref(m["desc"]), L.ptr(p.X), None, L.ptr(p.dYm), L.ptr(m["wpart"]), st)
-        L.call("mc_conv2d_wgrad_finalize", C.byref(m["desc"]), L.ptr(m["wpart"]), L.ptr(dws["conv"]), L.ptr(db), st)
-        L.call("mc_pack_weights", C.byref(m["desc"]), L.ptr(ws["conv"]), 1, L.ptr(m["dbank"]), st)
-        L.call("mc_conv2d", C.byref(m["ddesc"]), L.ptr(p.dYm), None, L.ptr(m["dbank"]), None, L.ptr(p.dXP), None, None, st)
-        for name, e in p.strips.items():
-            sy, sx, sh, sw, dy, dx = e["reg"]
-            L.call("mc_rect_copy", L.ptr(p.dY), H, W, dy, dx, L.ptr(e["dR"]), e["ho"], e["wo"], 0, 0, e["ho"], e["wo"], N, p.c_o, 0,
-                   p.mc, st)
-            L.call("mc_conv2d_wgrad", C.byref(e["desc"]), L.ptr(e["S"]), None, L.ptr(e["dR"]), L.ptr(e["wpart"]), st)
-            L.call("mc_conv2d_wgrad_finalize", C.byref(e["desc"]), L.ptr(e["wpart"]), L.ptr(dws[name]), L.ptr(db), st)
-            L.call("mc_pack_weights", C.byref(e["desc"]), L.ptr(ws[name]), 1, L.ptr(e["dbank"]), st)
-            L.call("mc_conv2d", C.byref(e["ddesc"]), L.ptr(e["dR"]), None, L.ptr(e["dbank"]), None, L.ptr(e["dS"]), None, None, st)
-            L.call("mc_rect_copy", L.ptr(e["dS"]), sh, sw, 0, 0, L.ptr(p.dXP), H + 2 * f, W + 2 * f, sy + f, sx + f, sh, sw, N,
-                   p.c_i, 1, p.mc, st)
-        L.call("mc_rect_copy", L.ptr(p.dXP), H + 2 * f, W + 2 * f, f, f, L.ptr(p.dX), H, W, 0, 0, H, W, N, p.c_i, 0, p.mc, st)
+        L.call("mc_conv2d_wgrad", C.byref(p.desc), L.ptr(p.X), None, L.ptr(p.dR), L.ptr(p.wpart), st)
+        L.call("mc_conv2d_wgrad_finalize", C.byref(p.desc), L.ptr(p.wpart), L.ptr(dws["conv"]), L.ptr(db), st)
+        L.call("mc_learned_frame_wgrad", C.byref(p.ld), L.ptr(p.X), L.ptr(p.dY), L.ptr(p.lws),
+               (C.c_void_p * 8)(*[L.ptr(dws[n]) for n in L.LEARNED_FRAME_BANKS]), L.ptr(db), st)
+        L.call("mc_conv2d", C.byref(p.ddesc), L.ptr(p.dR), None, L.ptr(p.dbank), None, L.ptr(p.dX), None, None, st)
+        L.call("mc_learned_frame_dgrad", C.byref(p.ld), L.ptr(p.dY), L.ptr(p.ldbank), L.ptr(p.dX), st)
         dx = torch.empty((N, p.c_i, H, W), dtype=torch.float32, device=dev)
         L.call("mc_unpack_nchw", L.ptr(p.dX), N, p.c_i, H, W, 0, None, p.mc, L.ptr(dx), st)
         gws = [dws[n] if dt == torch.float32 else dws[n].to(dt) for n, dt in zip(BANKS, ctx.wdtypes)]
