@@ -8,7 +8,6 @@ int mc_wgrad_f32(const ConvGeom& g, const void* x0, const void* x1, const void* 
 // bf16 MFMA path (conv_bf16.hip)
 int mc_bf16_tile(const mc_conv_desc* d, int* th, int* tw);
 size_t mc_bf16_bank_bytes(const ConvGeom& g, int dgrad);
-int mc_bf16_pack(const ConvGeom& g, const float* w_unique, int dgrad, void* packed, hipStream_t s);
 int mc_conv2d_bf16(const ConvGeom& g, const void* x0, const void* x1, const void* bank, const float* bias, void* y0,
                    void* y1, float* part, const ConvFuse& fz, int fuse, hipStream_t s);
 int mc_wgrad_bf16(const ConvGeom& g, const void* x0, const void* x1, const void* dy, void* part, const ConvFuse& fz, int fuse,
@@ -18,7 +17,6 @@ void mc_bf16_bank_dims(const ConvGeom& g, int dgrad, int& chunks, int& steps, in
 // row-reuse bf16 path for single-output-tile layers (conv_rr_bf16.hip)
 bool mc_rr_applies(int dtype, int cout, int wo, bool full_pad);
 size_t mc_rr_bank_bytes(const ConvGeom& g, int dgrad);
-int mc_rr_pack(const ConvGeom& g, const float* w_unique, int dgrad, void* packed, hipStream_t s);
 int mc_conv2d_rr(const ConvGeom& g, const void* x0, const void* x1, const void* bank, const float* bias, void* y0, void* y1,
                  float* part, const ConvFuse& fz, int fuse, hipStream_t s);
 const char* mc_rr_kernel_name(const ConvGeom& g, int fuse);
@@ -48,13 +46,8 @@ int geom_for(const mc_conv_desc* d, ConvGeom& g) {
 // partial-sum slots per sample the forward / input-gradient kernel writes (one per tile; per (tile, strip) for row reuse)
 int stat_slots(const mc_conv_desc* d, const ConvGeom& g) { return rr_desc(d) ? g.tiles * RR_STRIPS : g.tiles; }
 
-// f32 bank: [cbin][tap][ci8][CoutP]
-__global__ void k_pack_f32(ConvGeom g, const float* __restrict__ wu, int dgrad, float* __restrict__ bank, size_t total) {
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x)
-    bank[i] = pack_value_f32(g, wu, i, dgrad);
-}
-
-// ---- batched packing: the job table travels by value in the kernel arguments (<= PK_MAX jobs per launch)
+// ---- filter-bank packing: the job table travels by value in the kernel arguments (<= PK_MAX jobs per launch)
+// (f32 bank: [cbin][tap][ci8][CoutP]; the 16-bit banks: conv_bf16.hip, conv_rr.h)
 struct PkJob {
   int K, Cout, CBin, CB0, Cin0, Cin1, Cin, U, nh, nv, nq, CBout, CinP, CoutP;
   int dgrad, steps, ntiles, bf16, f16, rr, first_block;
@@ -216,21 +209,6 @@ size_t mc_packed_weight_bytes(const mc_conv_desc* d, int32_t dgrad) {
   if (mc_is16(g.dtype)) return mc_bf16_bank_bytes(g, dgrad);
   int cbin = dgrad ? g.CBout : g.CBin, cop = dgrad ? g.CinP : g.CoutP;
   return (size_t)cbin * g.K * g.K * 8 * cop * sizeof(float);
-}
-
-int mc_pack_weights(const mc_conv_desc* d, const float* w_unique, int32_t dgrad, void* packed, void* stream) {
-  ConvGeom g;
-  int rc = geom_for(d, g);
-  if (rc) return rc;
-  if (!w_unique || !packed) return MC_EINVAL;
-  if (bank_is_rr(g, dgrad)) return mc_rr_pack(g, w_unique, dgrad, packed, (hipStream_t)stream);
-  if (mc_is16(g.dtype)) return mc_bf16_pack(g, w_unique, dgrad, packed, (hipStream_t)stream);
-  size_t total = mc_packed_weight_bytes(d, dgrad) / sizeof(float);
-  int blocks = (int)((total + 255) / 256);
-  if (blocks > 2048) blocks = 2048;
-  hipLaunchKernelGGL(k_pack_f32, dim3(blocks), dim3(256), 0, (hipStream_t)stream, g, w_unique, dgrad, (float*)packed, total);
-  MC_CHECK_LAUNCH();
-  return MC_OK;
 }
 
 const char* mc_conv_kernel_name(const mc_conv_desc* d) {
@@ -424,6 +402,14 @@ int mc_pack_weights_batched(const mc_conv_desc* descs, const float* const* w_uni
     MC_CHECK_LAUNCH();
   }
   return MC_OK;
+}
+
+int mc_pack_weights(const mc_conv_desc* d, const float* w_unique, int32_t dgrad, void* packed, void* stream) {
+  ConvGeom g;
+  int rc = geom_for(d, g);
+  if (rc) return rc;
+  if (!w_unique || !packed) return MC_EINVAL;
+  return mc_pack_weights_batched(d, &w_unique, &dgrad, &packed, 1, stream);
 }
 
 }  // extern "C"

@@ -25,14 +25,6 @@ typedef unsigned int v4u __attribute__((ext_vector_type(4)));
 
 namespace {
 
-// XCD-aware work-group id: hardware deals consecutive blockIdx round-robin over the 8 XCDs (each with a private L2);
-// remap so that every XCD owns a CONTIGUOUS range of ids -> spatially adjacent tiles (which share their input halo)
-// run on the same XCD and the halo re-reads hit that XCD's L2.  Bijective for any grid size (speed only, never correctness).
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-  const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-}
-
 constexpr int CHUNK_CB = 2;     // 8-channel blocks per K-chunk (16 input channels)
 
 template <int K> struct KSteps { static constexpr int pairs = K * K * CHUNK_CB; static constexpr int steps = (pairs + 3) / 4; };
@@ -43,18 +35,10 @@ struct Bf16Cfg { int th, tw, nt, mt; };
 __host__ __device__ inline int pick_nt(int n_tiles) { return (n_tiles % 4 == 0) ? 4 : ((n_tiles % 2 == 0) ? 2 : 1); }
 
 // ------------------------------------------------------------------------------------------------
-// bank packing: bank[chunk][step][ntile][lane][8]  (bf16), lane = 16 g + n:
+// bank layout: bank[chunk][step][ntile][lane][8]  (bf16), lane = 16 g + n:
 //   element e of lane (n, g) at step s = W[co = ntile*16 + n][ci = chunk*16 + cb*8 + e][tap]
-//   with pair j = 4 s + g, tap = j / 2, cb = j % 2.
+//   with pair j = 4 s + g, tap = j / 2, cb = j % 2  (pack_value_bf16 in conv_common.h; packed by k_pack_batched).
 // ------------------------------------------------------------------------------------------------
-__global__ void k_pack_bf16(ConvGeom g, const float* __restrict__ wu, int dgrad, bf16_t* __restrict__ bank,
-                            int chunks, int steps, int ntiles, int f16) {
-  const size_t total = (size_t)chunks * steps * ntiles * 64 * 8;
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    const float v = pack_value_bf16(g, wu, i, dgrad, steps, ntiles);
-    bank[i] = f16 ? __builtin_bit_cast(bf16_t, (_Float16)v) : f2bf(v);
-  }
-}
 
 // H16 (MC_MIX16): FUSE 0 / 1 = forward convolution on f16 operands with an f16 output; FUSE 2 = input-gradient convolution
 // (bf16) whose epilogue reads the producer's raw output y as f16 (see conv_rr_bf16.hip)
@@ -76,11 +60,6 @@ template <bool H16> __device__ __forceinline__ f32x4 mfma16(bf16x8 a, bf16x8 b, 
 // pixel, row = 4*(lane>>4)+reg = channel): exactly 8 contiguous bytes of the CB8 output vector.  The
 // epilogue therefore stores straight from registers (no LDS transpose, no extra barriers).
 // ------------------------------------------------------------------------------------------------
-#ifdef MC_EXP_NOSYNC   /* timing experiment only: racy */
-#define MC_SYNC() do {} while (0)
-#else
-#define MC_SYNC() __syncthreads()
-#endif
 // FUSE: 0 = plain; 1 = prologue (the sources are raw conv outputs: GroupNorm affine + activation applied while the tile
 // is staged); 2 = input-gradient epilogue (dz = dA * act'(z) and the GroupNorm-backward partial sums instead of dA).
 // WN (wave columns): 1 = every wave owns MT M-tiles x all NT N-tiles of the block; 2 = the waves form a (WAVES / 2) x 2 grid,
@@ -89,10 +68,7 @@ template <bool H16> __device__ __forceinline__ f32x4 mfma16(bf16x8 a, bf16x8 b, 
 // fragments = 512 cycles per 12-MFMA step whose matrix-pipe share is 384; cycle stamps: 548); with WN = 2 a wave fetches half
 // of them for twice the pixels (2 fragments through the L1, 6 through LDS per 12 MFMAs).
 template <int K, int TH, int TW, int NT, int MT, bool OUT_F32 = false, int FUSE = 0, bool H16 = false, int WN = 1>
-#ifndef MC_CONV_WAVES
-#define MC_CONV_WAVES 2
-#endif
-__global__ __launch_bounds__(64 * (TH * (TW / 16) / MT) * WN, (MT * NT / WN <= 8 ? MC_CONV_WAVES : 2)) void k_conv_mfma_bf16(
+__global__ __launch_bounds__(64 * (TH * (TW / 16) / MT) * WN, 2) void k_conv_mfma_bf16(
     ConvGeom g, const bf16_t* __restrict__ x0, const bf16_t* __restrict__ x1, const bf16_t* __restrict__ bank,
     const float* __restrict__ bias, bf16_t* __restrict__ y0, bf16_t* __restrict__ y1, float* __restrict__ part,
     int n_groups, ConvFuse fz) {
@@ -107,10 +83,7 @@ __global__ __launch_bounds__(64 * (TH * (TW / 16) / MT) * WN, (MT * NT / WN <= 8
   // NT == 1: the bank slice (13 KiB) is staged in LDS once per chunk.  NT > 1 (deep, channel-heavy layers): the slice
   // would be 27-53 KiB per chunk and re-staging it dominated the per-workgroup critical path, so B fragments are read
   // straight from the L2-resident bank (each lane's fragment is one contiguous 16-byte load) a K-step ahead.
-#ifndef MC_WGLOBAL_ALL
-#define MC_WGLOBAL_ALL 0
-#endif
-  constexpr bool WGLOBAL = NT > 1 || MC_WGLOBAL_ALL;
+  constexpr bool WGLOBAL = NT > 1;
   constexpr int W_SLOTS = WGLOBAL ? 0 : STEPS * NT * 64;
   static_assert(!OUT_F32 || NT == 1, "f32 output is for the single-N-tile configuration");
   constexpr int IN_ELEMS = CHUNK_CB * TIH * TIW;
@@ -195,11 +168,7 @@ __global__ __launch_bounds__(64 * (TH * (TW / 16) / MT) * WN, (MT * NT / WN <= 8
           off = (oky && okx) ? (unsigned)(sy * g.W + sx) * 16u : 0xFFFFFFF0u;
           if (FUSE == 1 && cb == 0 && !(oky && okx)) okm &= ~(1u << it);
         }
-#ifdef MC_EXP_NOLOAD   /* timing experiment only: wrong results */
-        rin[cb][it] = (v4u){off, off, off, off};
-#else
         rin[cb][it] = __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0);
-#endif
       }
     }
   };
@@ -255,10 +224,7 @@ __global__ __launch_bounds__(64 * (TH * (TW / 16) / MT) * WN, (MT * NT / WN <= 8
 
   // cross-stage register prefetch only where the register budget allows it (single N-tile configuration);
   // the wider configurations load and commit a stage back to back (their K loop is MT*NT MFMAs per fragment pair)
-#ifndef MC_PREFETCH_ALL
-#define MC_PREFETCH_ALL 0
-#endif
-  constexpr bool PREFETCH = (NT == 1) || MC_PREFETCH_ALL;
+  constexpr bool PREFETCH = NT == 1;
   f32x4 acc[MT][NTW];
   if (PREFETCH && total_stages > 0) prefetch(0);
 #ifdef MC_EXP_STAMPS   /* timing experiment only */
@@ -279,13 +245,13 @@ __global__ __launch_bounds__(64 * (TH * (TW / 16) / MT) * WN, (MT * NT / WN <= 8
         for (int tt = 0; tt < NTW; ++tt) acc[i][tt] = (f32x4){bv[tt][0], bv[tt][1], bv[tt][2], bv[tt][3]};   // bias folded in
     }
     if (!PREFETCH) prefetch(t);
-    MC_SYNC();                                            // LDS free: previous MFMA loop done
+    __syncthreads();                                      // LDS free: previous MFMA loop done
     STAMP(0);
     commit();
     if (!WGLOBAL && (chunks > 1 || t == 0)) stage_weights(ck);
     const uint4* wglob = reinterpret_cast<const uint4*>(bank) + ((size_t)ck * STEPS * ntiles_total + ntile0 + nt_w0) * 64 + lane;
     STAMP(1);
-    MC_SYNC();
+    __syncthreads();
     STAMP(2);
     if (PREFETCH && t + 1 < total_stages) prefetch(t + 1);      // in flight during the MFMA loop
     STAMP(3);
@@ -304,11 +270,7 @@ __global__ __launch_bounds__(64 * (TH * (TW / 16) / MT) * WN, (MT * NT / WN <= 8
 #pragma unroll
       for (int tt = 0; tt < NTW; ++tt) {
         if (WGLOBAL) {
-#ifdef MC_EXP_NOWLOAD   /* timing experiment only: wrong results */
-          uint4 wv = make_uint4(sidx, tt, lane, 0);
-#else
           uint4 wv = wglob[((size_t)sidx * ntiles_total + tt) * 64];
-#endif
           wf[tt] = __builtin_bit_cast(bf16x8, wv);
         } else {
           wf[tt] = *reinterpret_cast<const bf16x8*>(&w_s[(sidx * NT + tt) * 64 + lane]);
@@ -324,22 +286,14 @@ __global__ __launch_bounds__(64 * (TH * (TW / 16) / MT) * WN, (MT * NT / WN <= 8
 #pragma unroll
         for (int tt = 0; tt < NTW; ++tt) acc[i][tt] = mfma16<(H16 && FUSE != 2)>(wf[tt], xf[i], acc[i][tt]);
     };
-#ifndef MC_KPIPE
-#define MC_KPIPE 0
-#endif
-#ifndef MC_KUNROLL
-#define MC_KUNROLL 1    /* 1: the K loop of the L2-fed configurations fully unrolled; 0: rolled by two steps (A/B) */
-#endif
-    if constexpr (WGLOBAL && MC_KUNROLL) {
+    if constexpr (WGLOBAL) {
     // Fully unrolled: in the rolled form the fragment loads of the next step sit behind a loop-carried condition
     // (s + 1 < STEPS), so the compiler cannot know how many loads are outstanding at the MFMAs and waits for ALL of them
     // (s_waitcnt vmcnt(3..0) lgkmcnt(2..0) in front of the first MFMAs of every step: the loads issued one step ahead were
     // waited for at once).  With static step indices every wait counts exactly the older set (vmcnt(7) lgkmcnt(5));
-    // sched_barrier keeps the sets in program order (the scheduler otherwise hoists every step's loads).  -0.08 ms per step.
-#ifndef MC_KDEPTH
-#define MC_KDEPTH 2     /* fragment sets in the ring: the loads of step s + MC_KDEPTH - 1 are issued before the MFMAs of step s (3, 4: +-0) */
-#endif
-    constexpr int KD = MC_KDEPTH;
+    // sched_barrier keeps the sets in program order (the scheduler otherwise hoists every step's loads).  -0.08 ms per step
+    // against the form rolled by two steps.
+    constexpr int KD = 2;   // fragment sets in the ring: the loads of step s + KD - 1 are issued before the MFMAs of step s (3, 4: +-0)
     bf16x8 xr[KD][MT], wr[KD][NTW];
 #pragma unroll
     for (int s = 0; s < KD - 1 && s < STEPS; ++s) load_frags(s, xr[s], wr[s]);
@@ -350,34 +304,12 @@ __global__ __launch_bounds__(64 * (TH * (TW / 16) / MT) * WN, (MT * NT / WN <= 8
       do_mfma(xr[s % KD], wr[s % KD]);
       __builtin_amdgcn_sched_barrier(0);
     }
-    } else if constexpr (WGLOBAL || MC_KPIPE == 2) {
-    bf16x8 xa[MT], xb[MT], wa[NTW], wb[NTW];
-    load_frags(0, xa, wa);
-#pragma unroll 1
-    for (int s = 0; s < STEPS; s += 2) {
-      if (s + 1 < STEPS) load_frags(s + 1, xb, wb);
-      do_mfma(xa, wa);
-      if (s + 2 < STEPS) load_frags(s + 2, xa, wa);
-      if (s + 1 < STEPS) do_mfma(xb, wb);
-    }
     } else {
     bf16x8 xa[MT], wa[NTW];
 #pragma unroll 1
-#ifdef MC_EXP_NOK   /* timing experiment only */
-    for (int s = 0; s < 1; ++s) {
-#else
     for (int s = 0; s < STEPS; ++s) {
-#endif
       load_frags(s, xa, wa);
-#if MC_KPIPE == 1
-      // all fragment reads of the step first, each into its own registers, then the MFMAs: an MFMA waits only for ITS
-      // fragment (the default schedule reused one register quad and exposed the LDS latency before every MFMA)
-      __builtin_amdgcn_sched_group_barrier(0x100, MT + NTW, 0);
-#endif
       do_mfma(xa, wa);
-#if MC_KPIPE == 1
-      __builtin_amdgcn_sched_group_barrier(0x008, MT * NTW, 0);
-#endif
     }
     }
     STAMP(4);
@@ -424,11 +356,7 @@ __global__ __launch_bounds__(64 * (TH * (TW / 16) / MT) * WN, (MT * NT / WN <= 8
             s1[tt][0] += v01; s1[tt][1] += v23;
             s2[tt][0] = pk_fma(v01, v01, s2[tt][0]); s2[tt][1] = pk_fma(v23, v23, s2[tt][1]);
           }
-#ifdef MC_EXP_NOSTORE   /* timing experiment only */
-          if (inb && cobok[tt] && v01.x == 123.456f) {
-#else
           if (inb && cobok[tt]) {
-#endif
             if (OUT_F32) {
               *reinterpret_cast<float4*>(dst0[tt] + off) = make_float4(v01.x, v01.y, v23.x, v23.y);
             } else {
@@ -529,7 +457,7 @@ __global__ __launch_bounds__(64 * (TH * (TW / 16) / MT) * WN, (MT * NT / WN <= 8
         // value index = 4 b3 + 2 b2 + b1 = (channel r = idx >> 1, idx & 1 = sum / sum of squares)
         if ((m & 1) == 0) red[wave][((nt_w0 + tt) * 16 + gq * 4) * 2 + (m >> 1)] = q1;
       }
-      MC_SYNC();
+      __syncthreads();
       if (threadIdx.x < NT * 32) {
         int co = ntile0 * 16 + (threadIdx.x >> 1);
         if (co < g.CoutP) {
@@ -551,14 +479,13 @@ __global__ __launch_bounds__(64 * (TH * (TW / 16) / MT) * WN, (MT * NT / WN <= 8
 // ------------------------------------------------------------------------------------------------
 // filter gradient on the matrix cores:
 //   dW[co][ci][ky][kx] = sum_{n,oy,ox} dy[n][co][oy][ox] * xpad[n][ci][oy+ky][ox+kx]
-// as D[i = co][j = ci] += A[i][k] B[k][j] with k = 32 consecutive output pixels of one row, one MFMA per
+// as D[i = co][j = ci] += A[i][k] B[k][j] with k = 32 output pixels (4 rows x 8 columns), one MFMA per
 // (tap, co-tile) and k-group.  Both operands need the PIXEL index on the MFMA k axis while the CB8 tiles in
 // LDS hold 8 CHANNELS per 16-byte vector: the transposition is done by ds_read_b64_tr_b16 (4 pixels x 16
-// channels per 16-lane group, delivered channel-per-lane) — two reads per fragment, any tap shift stays
-// 16-byte aligned because a pixel step is a whole vector.  Plane strides are == 4 (mod 16) slots so the
-// two channel-block planes of a read land on disjoint banks.
+// channels per 16-lane group, delivered channel-per-lane); any tap shift stays 16-byte aligned because a
+// pixel step is a whole vector.
 //
-// Block (G, chunk, co-group): loops over (image, 16x32-pixel tile) work items; wave w owns taps w, w+4, ...
+// Block (G, chunk, co-group): loops over (image, 16x32-pixel tile) work items; wave w owns tap group w
 // (7/6/6/6 of 25) for NTW co-tiles; wave 3 also accumulates the bias gradient through an all-ones B fragment.
 // Partials: [G] slabs (layout: wg_index in conv_common.h), combined deterministically by k_wgrad_finalize.
 // ------------------------------------------------------------------------------------------------
@@ -573,73 +500,53 @@ __device__ __forceinline__ bf16x8 tr_frag(const short* base_lo) {
 }
 
 constexpr int WTH = 16, WTW = 32;      // work-item tile (output pixels)
-#ifndef MC_WGRAD_BATCH_NTW
-#define MC_WGRAD_BATCH_NTW 1          // batch the tap-fragment reads of a row for NTW >= this (3 = never, 1 = always)
-#endif
 
-// RS ("register shift", RS != 0): the K dimension of an MFMA is 4 rows x 8 pixels instead of 32 pixels of a row, so
-// the B fragments of the K taps of a filter row are windows [kx, kx+8) of the SAME 12 pixels of a lane: three
-// transposing reads + 8 v_alignbit feed 5 MFMAs (0.7-0.85 LDS reads per MFMA instead of 2.3; the kernel was LDS-issue
-// bound).  RS = number of tap groups the 25 taps are split into: wave = (tap group tg = wave % RS, column group
-// wave / RS of RS 8-column blocks).  RS 1: all taps + bias, one column block (26 NTW accumulators); RS 2: 13/12 taps,
-// two column blocks; RS 4: 7/6/6/6 taps, the whole tile (no cross-wave sum).  The bias gradient rides in the spare
-// slot of the last tap group.  Column groups are summed through LDS once per workgroup.
+// Register shift: the K dimension of an MFMA is 4 rows x 8 pixels instead of 32 pixels of a row, so the B fragments of
+// the K taps of a filter row are windows [kx, kx+8) of the SAME 12 pixels of a lane: three transposing reads + 8
+// v_alignbit feed 5 MFMAs (0.7-0.85 LDS reads per MFMA instead of 2.3; the kernel was LDS-issue bound).  The taps are
+// split into four groups, one per wave (7/6/6/6 of 25), and every wave covers the whole tile, so nothing is summed across
+// waves.  The bias gradient rides in the spare slot of the last tap group.
+// This is the one form left of four: measured alone at level 0 (16->16, 32x506x512), the row-at-a-time kernel took 266 us,
+// 1 / 2 / 4 tap groups 171 / 203 / 155 us (64->64 at 63x64: row-at-a-time 44 us, 4 groups 37); inside the training step
+// they were equal (the filter gradients run on the side stream and are off the critical path).
 // PRO: x0 / x1 are raw conv outputs; the producer's GroupNorm affine + activation are applied while the tile is staged.
 // XH (MC_MIX16): x0 / x1 are f16 tensors of the forward pass, converted to bf16 while the tile is staged (dy is bf16).
-template <int K, int NTW, int RS, bool PRO = false, bool XH = false>
-__global__ __launch_bounds__(256, (NTW == 1 && RS >= 2) ? 3 : 2) void k_wgrad_mfma_bf16(ConvGeom g, const bf16_t* __restrict__ x0,
+template <int K, int NTW, bool PRO = false, bool XH = false>
+__global__ __launch_bounds__(256, NTW == 1 ? 3 : 2) void k_wgrad_mfma_bf16(ConvGeom g, const bf16_t* __restrict__ x0,
                                                             const bf16_t* __restrict__ x1, const bf16_t* __restrict__ dy,
                                                             float* __restrict__ part, int tiles_x, int tiles, ConvFuse fz) {
-  static_assert(RS == 0 || RS == 1 || RS == 2 || RS == 4, "tap groups");
-  constexpr int NS = RS ? RS : 1;                               // tap groups
-  constexpr int NG = 4 / NS;                                    // column groups (waves that share a tap group)
+  constexpr int NS = 4;                                         // tap groups = waves
   constexpr int TPW = (K * K + NS) / NS;                        // accumulator slots of a wave (last group: + bias)
   constexpr int KK = K * K;
   constexpr int TIH = WTH + K - 1, TIW = WTW + K - 1;
-  // RS: row strides == 4 and plane strides == 8 (mod 16 slots) make the 4 row groups x 2 planes of a transposing read
+  // row strides == 4 and plane strides == 8 (mod 16 slots) make the 4 row groups x 2 planes of a transposing read
   // hit 8 distinct bank quads
-  constexpr int XRS = RS ? (TIW + 11) / 16 * 16 + 4 : TIW;    // x row stride (slots)
-  constexpr int DRS = RS ? WTW + 4 : WTW;                     // dy row stride (slots)
-  constexpr int XPS = RS ? (TIH * XRS + 15) / 16 * 16 + 8 : ((TIH * TIW + 15) / 16) * 16 + 4;   // x plane stride (slots)
-  constexpr int DPS = RS ? WTH * DRS + 8 : WTH * WTW + 4;     // dy plane stride (slots)
-  static_assert(!RS || (XRS >= TIW && XRS >= 3 * 8 + 12 && XRS % 16 == 4 && DRS % 16 == 4 && XPS % 16 == 8 && DPS % 16 == 8),
+  constexpr int XRS = (TIW + 11) / 16 * 16 + 4;               // x row stride (slots)
+  constexpr int DRS = WTW + 4;                                // dy row stride (slots)
+  constexpr int XPS = (TIH * XRS + 15) / 16 * 16 + 8;         // x plane stride (slots)
+  constexpr int DPS = WTH * DRS + 8;                          // dy plane stride (slots)
+  static_assert(XRS >= TIW && XRS >= 3 * 8 + 12 && XRS % 16 == 4 && DRS % 16 == 4 && XPS % 16 == 8 && DPS % 16 == 8,
                 "register-shift LDS layout");
-  constexpr int NTAP = (KK + 3) / 4;                          // taps per wave (upper bound)
-  constexpr int NACC = RS ? TPW * NTW : NTAP * NTW;            // [tap slot (+ bias)][co tile]
+  constexpr int NACC = TPW * NTW;                             // [tap slot (+ bias)][co tile]
   constexpr int X_ITERS = (TIH * TIW + 255) / 256;            // staging slots per thread and channel-block plane
   constexpr int D_ELEMS = NTW * 2 * WTH * WTW, D_ITERS = D_ELEMS / 256;
   static_assert(D_ELEMS % 256 == 0, "dy tile must divide evenly over the threads");
   __shared__ uint4 smem[2 * XPS + NTW * 2 * DPS];
-  static_assert(RS == 0 || RS == 4 || sizeof(smem) >= NS * NACC * 256 * sizeof(float), "cross-wave reduction reuses the tile buffers");
   uint4* const xs = smem;
   uint4* const ds = smem + 2 * XPS;
   const int chunk = blockIdx.y, cog = blockIdx.z;
   const int bid = xcd_remap(blockIdx.x, gridDim.x);
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // scalar: tap offsets live in SGPRs
+  const int lane = threadIdx.x & 63, tg = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave = tap group (scalar)
   const int q = (lane & 15) >> 2, p = lane & 3, gq = lane >> 4;
-  // per-lane short offsets (2-byte units) inside a plane pair for pixel 8g + q of a row start
-  // (RS: pixel q of row gq of the wave's first 8-column block)
-  const int tg = wave % NS, cg = wave / NS;
-  const int col0 = 8 * NS * cg;
-  const int lane_x = RS ? ((p >> 1) * XPS + gq * XRS + col0 + q) * 8 + (p & 1) * 4 : ((p >> 1) * XPS + 8 * gq + q) * 8 + (p & 1) * 4;
-  const int lane_d = RS ? ((p >> 1) * DPS + gq * DRS + col0 + q) * 8 + (p & 1) * 4 : ((p >> 1) * DPS + 8 * gq + q) * 8 + (p & 1) * 4;
+  // per-lane short offsets (2-byte units) inside a plane pair for pixel q of row gq of the tile's first 8-column block
+  const int lane_x = ((p >> 1) * XPS + gq * XRS + q) * 8 + (p & 1) * 4;
+  const int lane_d = ((p >> 1) * DPS + gq * DRS + q) * 8 + (p & 1) * 4;
   const short* xs_s = reinterpret_cast<const short*>(xs);
   const short* ds_s = reinterpret_cast<const short*>(ds);
-  static_assert(3 + 4 * (NTAP - 1) >= KK, "wave 3 needs a free accumulator slot for the bias gradient");
-  const bool do_bias = (RS == 0 ? wave == 3 : tg == NS - 1) && (chunk == 0);
+  const bool do_bias = tg == NS - 1 && chunk == 0;
   const bf16x8 ones = (bf16x8){0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80};
   const ptrdiff_t x1_delta = x1 ? reinterpret_cast<const char*>(x1) - reinterpret_cast<const char*>(x0) : (ptrdiff_t)0;
 
-  // this wave's taps -> short offsets into the x tile (static over the whole kernel)
-  int toff[NTAP];
-#pragma unroll
-  for (int ti = 0; ti < NTAP; ++ti) {
-    int tap = wave + 4 * ti;
-    toff[ti] = tap < KK ? ((tap / K) * TIW + (tap % K)) * 8 : -1;
-  }
-  const short* xtap[NTAP];                                      // this lane's x-tile address per tap (row 0)
-#pragma unroll
-  for (int ti = 0; ti < NTAP; ++ti) xtap[ti] = xs_s + lane_x + max(toff[ti], 0);
   // static staging slots of this thread (decoded once: the staging address arithmetic was a third of the kernel's VALU work);
   // the two channel-block planes of the chunk use the same slots (the plane is uniform per load: scalar base, and the
   // producer's normalisation coefficients of a plane are uniform too)
@@ -770,191 +677,98 @@ __global__ __launch_bounds__(256, (NTW == 1 && RS >= 2) ? 3 : 2) void k_wgrad_mf
     for (int it = 0; it < D_ITERS; ++it) ds[d_lds0 + (it >> 1) * DPS + 8 * (it & 1) * DRS] = rd[it];
   };
 
-  f32x4 acc[NACC];                          // !RS: [tap slot][co tile]
+  f32x4 acc[NACC];
 #pragma unroll
   for (int a = 0; a < NACC; ++a) acc[a] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
   const int work = g.N * tiles;
   if (bid < work) prefetch(bid);
-  // The tap group of a wave is wave-uniform; the whole tile loop is instantiated per group (tg_c) and the branch sits
-  // OUTSIDE it: with the branch inside, the two arms' accumulators were allocated to disjoint registers (+52 VGPRs).
-  // Every arm executes the same sequence of workgroup barriers.
+  // The tap group of a wave is wave-uniform; the whole tile loop is instantiated per group (TG, a compile-time copy of tg
+  // that keeps the accumulators statically indexed) and the branch sits OUTSIDE it: with the branch inside, the two arms'
+  // accumulators were allocated to disjoint registers (+52 VGPRs).  Every arm executes the same sequence of workgroup
+  // barriers.
   auto tile_loop = [&](auto tg_c) __attribute__((always_inline)) {
-  for (int wi = bid; wi < work; wi += gridDim.x) {
-    __syncthreads();
-    commit();
-    __syncthreads();
-#ifndef MC_WEXP_NOLOAD   /* timing-only ablations (results wrong): MC_WEXP_NOLOAD, MC_WEXP_NOK */
-    if (wi + (int)gridDim.x < work) prefetch(wi + gridDim.x);   // next work item's loads retire under the MFMA loop
-#endif
-#ifdef MC_WEXP_NOK
-    if (g.N > 1000000)
-#endif
-#ifndef MC_WGRAD_ROW_UNROLL
-#define MC_WGRAD_ROW_UNROLL 2   /* A/B on MI355X: 2 and 4 equal within noise, 16 thrashes the instruction cache (70x slower) */
-#endif
-    if constexpr (RS != 0) {
-      typedef unsigned int u2 __attribute__((ext_vector_type(2)));
-      // TG is a compile-time copy of the wave-uniform tap group so that the accumulators stay statically indexed
-      auto body = [&](auto tg_c) __attribute__((always_inline)) {
-        constexpr int TG = decltype(tg_c)::value;
-        constexpr int T0 = TG == 0 ? 0 : TPW + (TG - 1) * (TPW - 1);
-        constexpr int T1 = (TPW + TG * (TPW - 1)) < KK ? (TPW + TG * (TPW - 1)) : KK;
-        static_assert(TG < NS - 1 || (T1 == KK && T1 - T0 < TPW), "the last tap group ends the filter and has a spare slot");
+    typedef unsigned int u2 __attribute__((ext_vector_type(2)));
+    constexpr int TG = decltype(tg_c)::value;
+    constexpr int T0 = TG == 0 ? 0 : TPW + (TG - 1) * (TPW - 1);
+    constexpr int T1 = (TPW + TG * (TPW - 1)) < KK ? (TPW + TG * (TPW - 1)) : KK;
+    static_assert(TG < NS - 1 || (T1 == KK && T1 - T0 < TPW), "the last tap group ends the filter and has a spare slot");
+    for (int wi = bid; wi < work; wi += gridDim.x) {
+      __syncthreads();
+      commit();
+      __syncthreads();
+      if (wi + (int)gridDim.x < work) prefetch(wi + gridDim.x);   // next work item's loads retire under the MFMA loop
 #pragma unroll
-        for (int rg = 0; rg < WTH / 4; ++rg) {                  // K block = rows 4rg..4rg+3 x an 8-column block
+      for (int rg = 0; rg < WTH / 4; ++rg) {                  // K block = rows 4rg..4rg+3 x an 8-column block
 #pragma unroll
-          for (int cb = 0; cb < NS; ++cb) {
-            const short* dp = ds_s + lane_d + (rg * 4 * DRS + cb * 8) * 8;
-            bf16x8 a[NTW];
+        for (int cb = 0; cb < WTW / 8; ++cb) {
+          const short* dp = ds_s + lane_d + (rg * 4 * DRS + cb * 8) * 8;
+          bf16x8 a[NTW];
 #pragma unroll
-            for (int t = 0; t < NTW; ++t) a[t] = tr_frag(dp + t * 2 * DPS * 8);
+          for (int t = 0; t < NTW; ++t) a[t] = tr_frag(dp + t * 2 * DPS * 8);
 #pragma unroll
-            for (int ky = 0; ky < K; ++ky) {
-              if (ky * K + K <= T0 || ky * K >= T1) continue;   // no tap of this filter row belongs to the wave
-              const short* xp = xs_s + lane_x + ((rg * 4 + ky) * XRS + cb * 8) * 8;
-              // 12 pixels of this lane's (row, channel) as 6 packed dwords
-              const u2 b0 = __builtin_bit_cast(u2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)xp));
-              const u2 b1 = __builtin_bit_cast(u2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)(xp + 32)));
-              const u2 b2 = __builtin_bit_cast(u2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)(xp + 64)));
-              const unsigned d[6] = {b0[0], b0[1], b1[0], b1[1], b2[0], b2[1]};
+          for (int ky = 0; ky < K; ++ky) {
+            if (ky * K + K <= T0 || ky * K >= T1) continue;   // no tap of this filter row belongs to the wave
+            const short* xp = xs_s + lane_x + ((rg * 4 + ky) * XRS + cb * 8) * 8;
+            // 12 pixels of this lane's (row, channel) as 6 packed dwords
+            const u2 b0 = __builtin_bit_cast(u2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)xp));
+            const u2 b1 = __builtin_bit_cast(u2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)(xp + 32)));
+            const u2 b2 = __builtin_bit_cast(u2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)(xp + 64)));
+            const unsigned d[6] = {b0[0], b0[1], b1[0], b1[1], b2[0], b2[1]};
 #pragma unroll
-              for (int kx = 0; kx < K; ++kx) {
-                const int tap = ky * K + kx;
-                if (tap < T0 || tap >= T1) continue;
-                v4u w;
-                if (kx % 2 == 0) {
-                  w = (v4u){d[kx / 2], d[kx / 2 + 1], d[kx / 2 + 2], d[kx / 2 + 3]};
-                } else {
+            for (int kx = 0; kx < K; ++kx) {
+              const int tap = ky * K + kx;
+              if (tap < T0 || tap >= T1) continue;
+              v4u w;
+              if (kx % 2 == 0) {
+                w = (v4u){d[kx / 2], d[kx / 2 + 1], d[kx / 2 + 2], d[kx / 2 + 3]};
+              } else {
 #pragma unroll
-                  for (int j = 0; j < 4; ++j) w[j] = __builtin_amdgcn_alignbit(d[kx / 2 + j + 1], d[kx / 2 + j], 16);
-                }
-#pragma unroll
-                for (int t = 0; t < NTW; ++t)
-                  acc[(tap - T0) * NTW + t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[t], __builtin_bit_cast(bf16x8, w), acc[(tap - T0) * NTW + t], 0, 0, 0);
+                for (int j = 0; j < 4; ++j) w[j] = __builtin_amdgcn_alignbit(d[kx / 2 + j + 1], d[kx / 2 + j], 16);
               }
-            }
-            if (TG == NS - 1 && do_bias) {
 #pragma unroll
               for (int t = 0; t < NTW; ++t)
-                acc[(TPW - 1) * NTW + t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[t], ones, acc[(TPW - 1) * NTW + t], 0, 0, 0);
+                acc[(tap - T0) * NTW + t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[t], __builtin_bit_cast(bf16x8, w), acc[(tap - T0) * NTW + t], 0, 0, 0);
             }
-#ifndef MC_WGRAD_NOFENCE
-            if constexpr (NS > 1) __builtin_amdgcn_sched_barrier(0);   // keep the scheduler from hoisting every block's reads (spills)
-#endif
           }
-        }
-      };
-      body(tg_c);
-    } else {
-    // rows unrolled so that the row offsets become instruction immediates (the loop was VALU-issue bound on address adds)
-#pragma unroll MC_WGRAD_ROW_UNROLL
-    for (int row = 0; row < WTH; ++row) {
-      bf16x8 a[NTW];
+          if (TG == NS - 1 && do_bias) {
 #pragma unroll
-      for (int t = 0; t < NTW; ++t) a[t] = tr_frag(ds_s + lane_d + (t * 2 * DPS + row * WTW) * 8);
-      if constexpr (NTW >= MC_WGRAD_BATCH_NTW) {
-        // read all of the row's tap fragments first so the MFMAs run back to back: -11 % on the 64-channel
-        // layers (NTW == 2, already at 2 waves/SIMD).  On NTW == 1 it costs a wave of occupancy and the level-0
-        // kernel alone gets 20 % slower, but inside the step (wgrad overlapped on the side stream) the whole step
-        // was still 0.05-0.1 ms faster in 3-way A/B, so it is on for both.
-        bf16x8 bq[NTAP];
-#pragma unroll
-        for (int ti = 0; ti < NTAP; ++ti) bq[ti] = tr_frag(xtap[ti] + row * TIW * 8);
-#pragma unroll
-        for (int ti = 0; ti < NTAP; ++ti) {
-          if (toff[ti] >= 0) {
-#pragma unroll
-            for (int t = 0; t < NTW; ++t) acc[ti * NTW + t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[t], bq[ti], acc[ti * NTW + t], 0, 0, 0);
+            for (int t = 0; t < NTW; ++t)
+              acc[(TPW - 1) * NTW + t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[t], ones, acc[(TPW - 1) * NTW + t], 0, 0, 0);
           }
-        }
-      } else {
-#pragma unroll
-        for (int ti = 0; ti < NTAP; ++ti) {
-          if (toff[ti] >= 0) {
-            bf16x8 b = tr_frag(xtap[ti] + row * TIW * 8);
-#pragma unroll
-            for (int t = 0; t < NTW; ++t) acc[ti * NTW + t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[t], b, acc[ti * NTW + t], 0, 0, 0);
-          }
+          __builtin_amdgcn_sched_barrier(0);   // keep the scheduler from hoisting every block's reads (spills)
         }
       }
-      if (do_bias) {
-#pragma unroll
-        for (int t = 0; t < NTW; ++t)
-          acc[(NTAP - 1) * NTW + t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[t], ones, acc[(NTAP - 1) * NTW + t], 0, 0, 0);
-      }
     }
-    }
-  }
   };
-  if constexpr (NS == 1) tile_loop(std::integral_constant<int, 0>{});
-  else if constexpr (NS == 2) { if (tg == 0) tile_loop(std::integral_constant<int, 0>{}); else tile_loop(std::integral_constant<int, 1>{}); }
-  else {
-    if (tg == 0) tile_loop(std::integral_constant<int, 0>{}); else if (tg == 1) tile_loop(std::integral_constant<int, 1>{});
-    else if (tg == 2) tile_loop(std::integral_constant<int, 2>{}); else tile_loop(std::integral_constant<int, 3>{});
-  }
+  if (tg == 0) tile_loop(std::integral_constant<int, 0>{}); else if (tg == 1) tile_loop(std::integral_constant<int, 1>{});
+  else if (tg == 2) tile_loop(std::integral_constant<int, 2>{}); else tile_loop(std::integral_constant<int, 3>{});
   // ---- write this block's partial slab: P[tap][chunk][co][16] (+ bias); a 16-lane group stores 64 contiguous bytes
   const int nch = wg_chunks(g.CinP);
   float* pb = part + (size_t)bid * wg_slab_floats(g.CoutP, g.CinP, KK);
-  if constexpr (RS != 0) {
-    // column groups 1.. hand their accumulators to group 0 through the (now idle) tile buffers, one group per round
-    f32x4* red = reinterpret_cast<f32x4*>(smem);
-    for (int src = 1; src < NG; ++src) {
-      __syncthreads();
-      if (cg == src) {
+  const int t0 = tg == 0 ? 0 : TPW + (tg - 1) * (TPW - 1);
+  const int nt = min(KK, TPW + tg * (TPW - 1)) - t0;
 #pragma unroll
-        for (int a = 0; a < NACC; ++a) red[(tg * NACC + a) * 64 + lane] = acc[a];
-      }
-      __syncthreads();
-      if (cg == 0) {
-#pragma unroll
-        for (int a = 0; a < NACC; ++a) acc[a] += red[(tg * NACC + a) * 64 + lane];
-      }
-    }
-    if (cg != 0) return;
-    const int t0 = tg == 0 ? 0 : TPW + (tg - 1) * (TPW - 1);
-    const int nt = min(KK, TPW + tg * (TPW - 1)) - t0;
-#pragma unroll
-    for (int sl = 0; sl < TPW; ++sl)
-#pragma unroll
-      for (int t = 0; t < NTW; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          int co = (cog * NTW + t) * 16 + gq * 4 + r;
-          if (sl < nt && co < g.CoutP) pb[((size_t)((t0 + sl) * nch + chunk) * g.CoutP + co) * 16 + (lane & 15)] = acc[sl * NTW + t][r];
-        }
-    if (do_bias && (lane & 15) == 0) {
-#pragma unroll
-      for (int t = 0; t < NTW; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          int co = (cog * NTW + t) * 16 + gq * 4 + r;
-          if (co < g.CoutP) pb[(size_t)KK * nch * g.CoutP * 16 + co] = acc[(TPW - 1) * NTW + t][r];
-        }
-    }
-    return;
-  }
-#pragma unroll
-  for (int ti = 0; ti < NTAP; ++ti) {
-    int tap = wave + 4 * ti;
+  for (int sl = 0; sl < TPW; ++sl)
 #pragma unroll
     for (int t = 0; t < NTW; ++t)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         int co = (cog * NTW + t) * 16 + gq * 4 + r;
-        if (co >= g.CoutP) continue;
-        if (tap < KK) {
-          pb[((size_t)(tap * nch + chunk) * g.CoutP + co) * 16 + (lane & 15)] = acc[ti * NTW + t][r];
-        } else if (do_bias && ti == NTAP - 1 && (lane & 15) == 0) {
-          pb[(size_t)KK * nch * g.CoutP * 16 + co] = acc[ti * NTW + t][r];
-        }
+        if (sl < nt && co < g.CoutP) pb[((size_t)((t0 + sl) * nch + chunk) * g.CoutP + co) * 16 + (lane & 15)] = acc[sl * NTW + t][r];
+      }
+  if (do_bias && (lane & 15) == 0) {
+#pragma unroll
+    for (int t = 0; t < NTW; ++t)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        int co = (cog * NTW + t) * 16 + gq * 4 + r;
+        if (co < g.CoutP) pb[(size_t)KK * nch * g.CoutP * 16 + co] = acc[(TPW - 1) * NTW + t][r];
       }
   }
 }
 
-#ifndef MC_NT1_MT
-#define MC_NT1_MT 8     /* M-tiles per wave of the single-N-tile configuration: 8 -> 4 waves, 4 -> 8 waves per workgroup */
-#endif
+constexpr int NT1_MT = 8;   // M-tiles per wave of the single-N-tile configuration: 8 -> 4 waves, 4 -> 8 waves per workgroup
 // Tile height 12 (3 M-tiles per wave) where it covers the output rows with fewer padded rows than 16: the input gradients of
 // the deep levels run on the padded domain (35 rows at level 4: 3 x 12 instead of 3 x 16, 67 at level 3: 72 instead of 80,
 // 130 at level 2: 132 instead of 144).  K = 5, several N-tiles per block only.
@@ -962,7 +776,7 @@ inline Bf16Cfg cfg_for(int c_out, int k, int ho) {
   static const int th12 = getenv("MC_CONV_TH12") ? atoi(getenv("MC_CONV_TH12")) : 1;
   int ntiles = (c_out + 15) / 16;
   int nt = pick_nt(ntiles);
-  if (nt == 1) return {16, 32, 1, MC_NT1_MT};
+  if (nt == 1) return {16, 32, 1, NT1_MT};
   const bool t12 = th12 && k == 5 && (ho + 11) / 12 * 12 < (ho + 15) / 16 * 16;
   // (24-row tiles, 6 M-tiles per wave -- each filter fragment feeds 6 MFMAs instead of 3 or 4 -- measured +0.04 ms where they
   // cover the rows as tightly as 12 / 16 and +0.2 ms everywhere: fragment reuse is not what bounds these launches)
@@ -1006,18 +820,6 @@ size_t mc_bf16_bank_bytes(const ConvGeom& g, int dgrad) {
   return (size_t)chunks * steps * ntiles * 64 * 16;
 }
 
-int mc_bf16_pack(const ConvGeom& g, const float* w, int dgrad, void* packed, hipStream_t s) {
-  int chunks, steps, ntiles;
-  mc_bf16_bank_dims(g, dgrad, chunks, steps, ntiles);
-  size_t total = (size_t)chunks * steps * ntiles * 64 * 8;
-  int blocks = (int)((total + 255) / 256);
-  if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(k_pack_bf16, dim3(blocks), dim3(256), 0, s, g, w, dgrad, (bf16_t*)packed, chunks, steps, ntiles,
-                     (g.dtype == MC_MIX16 && !dgrad) ? 1 : 0);
-  MC_CHECK_LAUNCH();
-  return MC_OK;
-}
-
 const char* mc_bf16_kernel_name(const ConvGeom& g) {
   Bf16Cfg c = cfg_for(g.Cout, g.K, g.Ho);
   if (g.out_f32) return g.K == 5 ? "k_conv_mfma_bf16<5,16,32,1,8,true>" : "k_conv_mfma_bf16<3,16,32,1,8,true>";
@@ -1052,18 +854,17 @@ int mc_conv2d_bf16(const ConvGeom& g_in, const void* x0, const void* x1, const v
        else LAUNCH_F(K, TH, TW, NT, MT, false, 2, WN); } while (0)
 #define LAUNCH(K, TH, TW, NT, MT, F32) LAUNCH_W(K, TH, TW, NT, MT, F32, 1)
   // four N-tiles per block: the waves as a 2 x 2 grid (a wave owns twice the M-tiles and half of the N-tiles; see the kernel)
-  static const int wn2 = getenv("MC_CONV_WN") ? atoi(getenv("MC_CONV_WN")) : 2;
-#define LAUNCH4(K, TH, TW, MT) do { if (wn2 == 2) LAUNCH_W(K, TH, TW, 4, 2 * (MT), false, 2); else LAUNCH_W(K, TH, TW, 4, MT, false, 1); } while (0)
+#define LAUNCH4(K, TH, TW, MT) LAUNCH_W(K, TH, TW, 4, 2 * (MT), false, 2)
   if (g.out_f32) {
-    if (g.K == 5) LAUNCH(5, 16, 32, 1, MC_NT1_MT, true); else if (g.K == 3) LAUNCH(3, 16, 32, 1, MC_NT1_MT, true); else return MC_EUNSUPPORTED;
+    if (g.K == 5) LAUNCH(5, 16, 32, 1, NT1_MT, true); else if (g.K == 3) LAUNCH(3, 16, 32, 1, NT1_MT, true); else return MC_EUNSUPPORTED;
   } else if (g.K == 5) {
-    if (c.nt == 1) LAUNCH(5, 16, 32, 1, MC_NT1_MT, false);
+    if (c.nt == 1) LAUNCH(5, 16, 32, 1, NT1_MT, false);
     else if (c.th == 24) LAUNCH_W(5, 24, 16, 4, 6, false, 1);
     else if (c.th == 12) { if (c.nt == 2) LAUNCH(5, 12, 16, 2, 3, false); else LAUNCH4(5, 12, 16, 3); }
     else if (c.th == 8) { if (c.nt == 2) LAUNCH(5, 8, 16, 2, 2, false); else LAUNCH4(5, 8, 16, 2); }
     else if (c.nt == 2) LAUNCH(5, 16, 16, 2, 4, false); else LAUNCH4(5, 16, 16, 4);
   } else if (g.K == 3) {
-    if (c.nt == 1) LAUNCH(3, 16, 32, 1, MC_NT1_MT, false); else if (c.nt == 2) LAUNCH(3, 16, 16, 2, 4, false); else LAUNCH4(3, 16, 16, 4);
+    if (c.nt == 1) LAUNCH(3, 16, 32, 1, NT1_MT, false); else if (c.nt == 2) LAUNCH(3, 16, 16, 2, 4, false); else LAUNCH4(3, 16, 16, 4);
   } else {
     return MC_EUNSUPPORTED;
   }
@@ -1085,21 +886,14 @@ int mc_wgrad_bf16(const ConvGeom& g_in, const void* x0, const void* x1, const vo
   const int ntw = pick_nt(ntiles) >= 2 ? 2 : 1;      // two co-tiles per block keep LDS at 55 KB (2-3 blocks per CU)
   dim3 grid(g.wgrad_G, (g.CBin + 1) / 2, (ntiles + ntw - 1) / ntw);
   const bool xh = g.dtype == MC_MIX16;
-#define WLAUNCH_X(K, NTW, RS, PRO, XH)                                                                                 \
-  hipLaunchKernelGGL((k_wgrad_mfma_bf16<K, NTW, RS, PRO, XH>), grid, dim3(256), 0, s, g, (const bf16_t*)x0, (const bf16_t*)x1, \
+#define WLAUNCH_X(K, NTW, PRO, XH)                                                                                     \
+  hipLaunchKernelGGL((k_wgrad_mfma_bf16<K, NTW, PRO, XH>), grid, dim3(256), 0, s, g, (const bf16_t*)x0, (const bf16_t*)x1, \
                      (const bf16_t*)dy, (float*)part, tiles_x, tiles, fz)
-#define WLAUNCH_P(K, NTW, RS, PRO) do { if (xh) WLAUNCH_X(K, NTW, RS, PRO, true); else WLAUNCH_X(K, NTW, RS, PRO, false); } while (0)
-#define WLAUNCH(K, NTW, RS) do { if (fuse) WLAUNCH_P(K, NTW, RS, true); else WLAUNCH_P(K, NTW, RS, false); } while (0)
-  // A/B knob: two decimal digits = tap groups for (one co-tile, two co-tiles); 0 = the row-at-a-time kernel.  Measured
-  // alone at level 0 (16->16, 32x506x512): 0: 266 us, 1: 171, 2: 203, 4: 155; 64->64 at 63x64: 0: 44 us, 4: 37.  Inside
-  // the training step 10 / 14 / 44 are equal (the filter gradients run on the side stream and are off the critical path).
-  static const int rs = [] { const char* e = getenv("MC_WGRAD_RS"); return e ? atoi(e) : 44; }();
-  const int v = ntw == 1 ? rs / 10 : rs % 10;
-#define WPICK(K, NTW) do { if (v == 4) WLAUNCH(K, NTW, 4); else if (v == 2) WLAUNCH(K, NTW, 2); else if (v == 1 && NTW == 1) WLAUNCH(K, 1, 1); else WLAUNCH(K, NTW, 0); } while (0)
-  if (g.K == 5) { if (ntw == 1) WPICK(5, 1); else WPICK(5, 2); }
-  else if (g.K == 3) { if (ntw == 1) WPICK(3, 1); else WPICK(3, 2); }
+#define WLAUNCH_P(K, NTW, PRO) do { if (xh) WLAUNCH_X(K, NTW, PRO, true); else WLAUNCH_X(K, NTW, PRO, false); } while (0)
+#define WLAUNCH(K, NTW) do { if (fuse) WLAUNCH_P(K, NTW, true); else WLAUNCH_P(K, NTW, false); } while (0)
+  if (g.K == 5) { if (ntw == 1) WLAUNCH(5, 1); else WLAUNCH(5, 2); }
+  else if (g.K == 3) { if (ntw == 1) WLAUNCH(3, 1); else WLAUNCH(3, 2); }
   else return MC_EUNSUPPORTED;
-#undef WPICK
 #undef WLAUNCH
 #undef WLAUNCH_P
 #undef WLAUNCH_X

@@ -122,13 +122,21 @@ static inline int conv_geom(const mc_conv_desc* d, int tile_h, int tile_w, ConvG
   return MC_OK;
 }
 
+// XCD-aware work-group id: hardware deals consecutive blockIdx round-robin over the 8 XCDs (each with a private L2);
+// remap so that every XCD owns a CONTIGUOUS range of ids -> spatially adjacent tiles (which share their input halo)
+// run on the same XCD and the halo re-reads hit that XCD's L2.  Bijective for any grid size (speed only, never correctness).
+__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
+  const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+}
+
 // padded input-channel index of global input channel ci (concat: source 0 then source 1)
 static __host__ __device__ inline int cin_padded_index(int ci, int Cin0, int CB0) {
   return ci < Cin0 ? ci : CB0 * 8 + (ci - Cin0);
 }
 
 // ------------------------------------------------------------------------------------------------
-// filter-bank element generators shared by the single-layer and the batched pack kernels.
+// filter-bank element generators of the pack kernel (k_pack_batched in conv_api.hip).
 // G is any struct with the fields K, Cout, CBin, CB0, Cin0, Cin1, Cin, U, nh, nv, nq, CBout, CinP, CoutP.
 // Output channel co >= U is a mirrored copy of a unique filter (the reference's torch.cat order: x-flips of unique [0, nh),
 // y-flips of [nh, nh + nv), then the x-, y- and xy-flips of [nh + nv, nh + nv + nq); symmetric_layers_torch.py:118-136).

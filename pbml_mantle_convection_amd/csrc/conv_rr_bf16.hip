@@ -43,18 +43,6 @@ typedef unsigned int v4u __attribute__((ext_vector_type(4)));
 
 namespace {
 
-__device__ __forceinline__ int rr_xcd_remap(int bid, int nwg) {
-  const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-}
-
-__global__ void k_pack_rr(ConvGeom g, const float* __restrict__ wu, int dgrad, bf16_t* __restrict__ bank, int ntiles, size_t total, int f16) {
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    const float v = rr_pack_value(g, wu, i, dgrad, ntiles);
-    bank[i] = f16 ? __builtin_bit_cast(bf16_t, (_Float16)v) : f2bf(v);
-  }
-}
-
 // 16-bit element type of a launch.  H16 = false: bf16 everywhere.  H16 = true (MC_MIX16): FUSE 0 / 1 = a forward
 // convolution whose sources, filter bank and (16-bit) output are f16; FUSE 2 = an input-gradient convolution (bf16 operands
 // and output) whose epilogue reads the producer's raw output y as f16.
@@ -102,7 +90,7 @@ __global__ __launch_bounds__(512, 2) void k_conv_rr_bf16(ConvGeom g, const bf16_
 
   const int grp = blockIdx.y;                                                    // 16-channel output tile of this block
   const int ntiles_total = gridDim.y;
-  const int bid = rr_xcd_remap(blockIdx.x, gridDim.x);
+  const int bid = xcd_remap(blockIdx.x, gridDim.x);
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int chunks = (g.CBin + 1) / 2;
   const int items = g.N * g.tiles;
@@ -661,11 +649,7 @@ __global__ __launch_bounds__(512, 2) void k_conv_rr_bf16(ConvGeom g, const bf16_
             }
             const auto sx = __builtin_amdgcn_permlane16_swap(rr_pk<H16>(a01.x, a01.y), rr_pk<H16>(b01.x, b01.y), false, false);
             const auto sy = __builtin_amdgcn_permlane16_swap(rr_pk<H16>(a23.x, a23.y), rr_pk<H16>(b23.x, b23.y), false, false);
-#ifdef MC_RR_NOSTORE   /* timing-only ablation: wrong results */
-            if ((FULL || (colok && ty0 + r + (gq & 1) < g.Ho)) && sx[0] == 0x12345678u)
-#else
             if (FULL || (colok && ty0 + r + (gq & 1) < g.Ho))
-#endif
               *reinterpret_cast<uint4*>(dst16 + (size_t)r * row_bytes) = make_uint4(sx[0], sy[0], sx[1], sy[1]);
           }
         };
@@ -732,9 +716,6 @@ bool mc_rr_applies(int dtype, int cout, int wo, bool full_pad) {
   return on >= 2 && ntiles <= 8 && wo >= minw;
 }
 
-void mc_rr_tile(int* th, int* tw) { *th = RR_R; *tw = RR_TW; }
-int mc_rr_stat_slots(const ConvGeom& g) { return g.tiles * RR_STRIPS; }
-
 static void rr_bank_dims(const ConvGeom& g, int dgrad, int& chunks, int& ntiles, int& nfrag) {
   const int cb_in = dgrad ? g.CBout : g.CBin;
   const int c_out = dgrad ? g.CinP : g.Cout;
@@ -746,17 +727,6 @@ size_t mc_rr_bank_bytes(const ConvGeom& g, int dgrad) {
   int chunks, ntiles, nfrag;
   rr_bank_dims(g, dgrad, chunks, ntiles, nfrag);
   return (size_t)chunks * ntiles * nfrag * 64 * 16;
-}
-int mc_rr_pack(const ConvGeom& g, const float* w, int dgrad, void* packed, hipStream_t s) {
-  int chunks, ntiles, nfrag;
-  rr_bank_dims(g, dgrad, chunks, ntiles, nfrag);
-  const size_t total = (size_t)chunks * ntiles * nfrag * 64 * 8;
-  int blocks = (int)((total + 255) / 256);
-  if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(k_pack_rr, dim3(blocks), dim3(256), 0, s, g, w, dgrad, (bf16_t*)packed, ntiles, total,
-                     (g.dtype == MC_MIX16 && !dgrad) ? 1 : 0);
-  MC_CHECK_LAUNCH();
-  return MC_OK;
 }
 
 const char* mc_rr_kernel_name(const ConvGeom& g, int fuse) {

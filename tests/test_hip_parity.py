@@ -511,3 +511,59 @@ def test_newfluidnet_learned_padding_vs_golden(golden):
         if float(np.abs(ref).max()) < 1e-6:
             continue
         assert_close(p.grad, ref, atol=5e-4 * max(1.0, float(np.abs(ref).max())), rtol=3e-3, what="grad " + n)
+
+
+def test_single_pack_equals_batched_job():
+    """mc_pack_weights against the same bank packed as job k of one mc_pack_weights_batched call of 26 jobs (one more than a
+    launch's table of 24 holds), byte for byte, forward and input-gradient banks.  Job k of call r is case (k + r) mod 13, so
+    over the 13 calls every descriptor sits at every position, the launch boundary (23 | 24) and the second launch's tail
+    (25) included, with the other cases around it.  Every descriptor has N = 1 and h = 4: nothing but packing is launched."""
+    import ctypes as C
+    from pbml_mantle_convection_amd import _lib as L
+    lib = L.load()
+    st = L.stream()
+
+    def desc(ci0, ci1, co, k, w, dtype, sh=0, sv=0, shv=0):
+        return L.ConvDesc(1, 4, w, ci0, ci1, co, k, k // 2, 0, dtype, sh, 0, 0, sv, shv)
+
+    def name(d):
+        return lib.mc_conv_kernel_name(C.byref(d)).decode()
+
+    def dgrad_name(d):            # kernel of the input-gradient convolution that consumes d's input-gradient bank
+        dt = L.MC_BF16 if d.dtype == L.MC_MIX16 else d.dtype
+        return name(L.ConvDesc(1, 4, d.w, d.c_out, 0, d.c_in0 + d.c_in1, d.k, d.k - 1, 0, dt, 0, 0, 0, 0, 0))
+
+    cases = [desc(12, 0, 20, 3, 16, L.MC_F32)]
+    assert name(cases[0]).startswith("k_conv_direct_f32")
+    for dt in (L.MC_BF16, L.MC_MIX16):
+        wide, rrf, rrd = desc(16, 0, 32, 5, 16, dt, sh=8), desc(16, 0, 16, 5, 16, dt), desc(16, 0, 32, 5, 160, dt)
+        assert name(wide).startswith("k_conv_mfma_bf16") and dgrad_name(wide).startswith("k_conv_mfma_bf16")
+        assert name(rrf).startswith("k_conv_rr_bf16") and dgrad_name(rrf).startswith("k_conv_mfma_bf16")
+        assert dgrad_name(rrd).startswith("k_conv_rr_bf16")
+        cases += [wide, rrf, rrd]
+    for dt in (L.MC_F32, L.MC_BF16, L.MC_MIX16):
+        cases += [desc(8, 12, 32, 3, 16, dt), desc(8, 0, 24, 5, 16, dt, sh=4, sv=2, shv=4)]
+    NC, NJ = len(cases), 26
+    assert NC == 13 and NJ == 24 + 2
+    gen = torch.Generator().manual_seed(26)
+    ws = []
+    for d in cases:
+        u = d.c_out - d.sym_h // 2 - d.sym_v // 2 - 3 * (d.sym_hv // 4)
+        ws.append(torch.randn((u, d.c_in0 + d.c_in1, d.k, d.k), generator=gen).to(DEV).contiguous())
+    seen = set()
+    for dg in (0, 1):
+        nbytes = [lib.mc_packed_weight_bytes(C.byref(d), dg) for d in cases]
+        assert all(nb > 0 for nb in nbytes)
+        single = [torch.full((nb,), 0x55, dtype=torch.uint8, device=DEV) for nb in nbytes]
+        for d, w, b in zip(cases, ws, single):
+            L.call("mc_pack_weights", C.byref(d), L.ptr(w), dg, L.ptr(b), st)
+        for r in range(NC):
+            idx = [(k + r) % NC for k in range(NJ)]
+            outs = [torch.full((nbytes[i],), 0xAA, dtype=torch.uint8, device=DEV) for i in idx]
+            L.call("mc_pack_weights_batched", (L.ConvDesc * NJ)(*[cases[i] for i in idx]),
+                   (C.c_void_p * NJ)(*[L.ptr(ws[i]) for i in idx]), (C.c_int32 * NJ)(*([dg] * NJ)),
+                   (C.c_void_p * NJ)(*[L.ptr(o) for o in outs]), NJ, st)
+            for k, i in enumerate(idx):
+                assert torch.equal(outs[k], single[i]), (dg, r, k, i)
+                seen.add((dg, i, k))
+    assert all((dg, i, k) in seen for dg in (0, 1) for i in range(NC) for k in (0, 23, 24, 25))
