@@ -95,13 +95,45 @@ class NetGraph:
     input_grad: bool = False   # backward also produces the gradient w.r.t. the network input (single-layer graphs, tests)
 
 
-def _sym_h(c_o: int) -> int:
-    # FluidLayer: h = c_o/4 (c_o/2 if c_o <= 4), v = hv = 0 (reference pytorch_networks_convae.py:755-757)
+def fluid_sym_h(c_o: int) -> int:
+    """FluidLayer's mirrored filters: h = c_o/4 (c_o/2 if c_o <= 4), v = hv = 0 (reference pytorch_networks_convae.py:755-757)."""
     return int(c_o / 4) if c_o > 4 else int(c_o / 2)
 
 
-def _groups(c_o: int) -> int:
-    return int(c_o / min(4, c_o))   # :788
+def fluid_groups(c_o: int) -> int:
+    """FluidLayer's GroupNorm groups (reference :788)."""
+    return int(c_o / min(4, c_o))
+
+
+class _Builder:
+    """A graph under construction: the channel dict, the node list and the tensor-id counter (ids in call order of new())."""
+
+    def __init__(self, c_i, f, use_symm, learned=False):
+        self.ch: Dict[int, int] = {0: c_i}
+        self.nodes = []
+        self.f, self.use_symm, self.learned = f, use_symm, learned
+
+    def new(self, c):
+        tid = len(self.ch)
+        self.ch[tid] = c
+        return tid
+
+    def conv(self, name, srcs, c_out, post, gn_name, groups, *, k=None, pad=None, symm=None, pool=1, out=None, **bc):
+        """Appends a ConvNode: k x k (default f), 'same' padding unless `pad` says otherwise, output (then pooled output)
+        allocated here unless the caller passes `out`.  symm: mirrored filters, where the network uses them at all; by default
+        what the reference's heads do -- only as learned-padding layers (fixed padding: plain nn.Conv2d)."""
+        k = self.f if k is None else k
+        symm = self.learned if symm is None else symm
+        node = ConvNode(name, list(srcs), self.new(c_out) if out is None else out, c_out, k, k // 2 if pad is None else pad,
+                        fluid_sym_h(c_out) if (symm and self.use_symm) else 0, post, gn_name, groups, pool, learned=self.learned, **bc)
+        if pool > 1:
+            node.pooled = self.new(c_out)
+        self.nodes.append(node)
+        return node
+
+    def fluid(self, prefix, srcs, c_out, **kw):
+        """A FluidLayer: conv + GroupNorm + activation."""
+        return self.conv(prefix + "layers.0.", srcs, c_out, L.POST_GN_ACT, prefix + "layers.1.", fluid_groups(c_out), symm=True, **kw)
 
 
 def unet_graph(levels, c_i, c_h, c_o, *, act, r_p, use_symm, repeats, f) -> NetGraph:
@@ -110,38 +142,27 @@ def unet_graph(levels, c_i, c_h, c_o, *, act, r_p, use_symm, repeats, f) -> NetG
     by the same 3 + 3 columns (:1990-1997) — and the two-operand concats are materialised (CatNode).  With fixed padding a
     two-operand concat is the conv's two sources, unless its first operand does not fill whole channel blocks (c_h = 6, 12,
     ...: the two-source conv kernels need c_in0 % 8 == 0); that concat is materialised too."""
+    if levels < 2:
+        raise ValueError("Unet needs levels >= 2")
     learned = r_p == "learned"
-    ch: Dict[int, int] = {0: c_i}
-    nodes = []
-    nid = [0]
-
-    def new(c):
-        nid[0] += 1
-        ch[nid[0]] = c
-        return nid[0]
+    b = _Builder(c_i, f, use_symm, learned)
+    ch, nodes = b.ch, b.nodes
 
     def one_src(srcs):
         if len(srcs) == 1 or (not learned and all(ch[i] % 8 == 0 for i in srcs[:-1])):
             return list(srcs)
-        cat = new(sum(ch[i] for i in srcs))
+        cat = b.new(sum(ch[i] for i in srcs))
         nodes.append(CatNode(list(srcs), cat))
         return [cat]
 
-    def fluid(prefix, srcs, c_out, pool=1, bc_x=1):
-        srcs = one_src(srcs)
-        out = new(c_out)
-        node = ConvNode(prefix + "layers.0.", list(srcs), out, c_out, f, f // 2, _sym_h(c_out) if use_symm else 0,
-                        L.POST_GN_ACT, prefix + "layers.1.", _groups(c_out), pool, learned=learned, bc_x=bc_x)
-        if pool > 1:
-            node.pooled = new(c_out)
-        nodes.append(node)
-        return node
+    def fluid(prefix, srcs, c_out, **kw):
+        return b.fluid(prefix, one_src(srcs), c_out, **kw)
 
     feat = {}
     cur = 0
     for r in range(repeats):
         last = r == repeats - 1
-        n = fluid(f"conv.{r}.", [cur], c_h, pool=2 if (last and levels > 1) else 1, bc_x=4 if (learned and r == 0) else 1)
+        n = fluid(f"conv.{r}.", [cur], c_h, pool=2 if last else 1, bc_x=4 if (learned and r == 0) else 1)
         cur = n.out
     feat[0] = n
     c = c_h
@@ -156,7 +177,7 @@ def unet_graph(levels, c_i, c_h, c_o, *, act, r_p, use_symm, repeats, f) -> NetG
     c = int(c / 2)
     xu = feat[levels - 1].out
     for li, l in enumerate(range(levels - 2, 0, -1)):
-        up = new(ch[xu])
+        up = b.new(ch[xu])
         nodes.append(UpNode(xu, up, like=feat[l].out))
         srcs = [feat[l].out, up]
         for r in range(repeats):
@@ -164,21 +185,15 @@ def unet_graph(levels, c_i, c_h, c_o, *, act, r_p, use_symm, repeats, f) -> NetG
             srcs = [n.out]
         xu = n.out
         c = int(c / 2)
-    if levels > 1:
-        up = new(ch[xu])
-        nodes.append(UpNode(xu, up, like=feat[0].out))
-        head_srcs = [up, feat[0].out]
-    else:
-        raise ValueError("Unet needs levels >= 2")
+    up = b.new(ch[xu])
+    nodes.append(UpNode(xu, up, like=feat[0].out))
     R = repeats
 
     def head(name, srcs, c_out, post, gn_name, groups):
-        o = new(c_out)
-        nodes.append(ConvNode(name, one_src(srcs), o, c_out, f, f // 2, (_sym_h(c_out) if use_symm else 0) if learned else 0,
-                              post, gn_name, groups, learned=learned))
-        return o
+        o = b.new(c_out)                     # (the head's output id precedes its concat's)
+        return b.conv(name, one_src(srcs), c_out, post, gn_name, groups, out=o).out
 
-    o = head(f"conv.{R}.", head_srcs, c, L.POST_GN_ACT, "gn.0.", int(c / 4))
+    o = head(f"conv.{R}.", [up, feat[0].out], c, L.POST_GN_ACT, "gn.0.", int(c / 4))
     o2 = head(f"conv.{R + 1}.", [o], c, L.POST_ACT, None, 1)
     head(f"conv.{R + 2}.", [o2], c_o, L.POST_NONE, None, 1)
     return NetGraph(c_i, c_o, ch, nodes, in_pad_w=0 if learned else 3, crop_w=3, subtract_mean=True,
@@ -188,30 +203,18 @@ def unet_graph(levels, c_i, c_h, c_o, *, act, r_p, use_symm, repeats, f) -> NetG
 def convae_graph(levels, c_i, c_h, c_o, *, act, r_p, use_symm, repeats, f, loss_type) -> NetGraph:
     """ConvAE.__init__ (reference .ipynb_checkpoints/pycold-checkpoint.py:1038-1092); returns the graph and
     keeps the ModuleList indices of the reference (pool / upsample modules consume an index)."""
-    ch: Dict[int, int] = {0: c_i}
-    nodes = []
-    nid = [0]
+    b = _Builder(c_i, f, use_symm)
     idx = [0]
 
-    def new(c):
-        nid[0] += 1
-        ch[nid[0]] = c
-        return nid[0]
-
     def fluid(src, c_out):
-        out = new(c_out)
-        p = f"conv.{idx[0]}."
         idx[0] += 1
-        node = ConvNode(p + "layers.0.", [src], out, c_out, f, f // 2, _sym_h(c_out) if use_symm else 0,
-                        L.POST_GN_ACT, p + "layers.1.", _groups(c_out))
-        nodes.append(node)
-        return node
+        return b.fluid(f"conv.{idx[0] - 1}.", [src], c_out)
 
     n = fluid(0, c_h)
     c = c_h
     for _ in range(levels):
         n.pool = 4
-        n.pooled = new(n.c_out)
+        n.pooled = b.new(n.c_out)
         idx[0] += 1                       # the AvgPool2d module
         cur = n.pooled
         cout = c * 4
@@ -225,8 +228,8 @@ def convae_graph(levels, c_i, c_h, c_o, *, act, r_p, use_symm, repeats, f, loss_
         n = fluid(cur, c)
         cur = n.out
     for _ in range(levels, 0, -1):
-        up = new(ch[cur])
-        nodes.append(UpNode(cur, up, scale=4))
+        up = b.new(b.ch[cur])
+        b.nodes.append(UpNode(cur, up, scale=4))
         idx[0] += 1                       # the Upsample module
         cur = up
         cout = int(c / 4)
@@ -234,78 +237,59 @@ def convae_graph(levels, c_i, c_h, c_o, *, act, r_p, use_symm, repeats, f, loss_
             n = fluid(cur, cout)
             cur = n.out
         c = int(c / 4)
-    o = new(c_o)
-    nodes.append(ConvNode(f"conv.{idx[0]}.", [cur], o, int(c_o), 3, 2 if loss_type == "curl" else 1, 0, L.POST_NONE,
-                          None, 1))
-    return NetGraph(c_i, int(c_o), ch, nodes, pad_mode=r_p, act=act, divisor=4 ** levels)
+    b.conv(f"conv.{idx[0]}.", [cur], int(c_o), L.POST_NONE, None, 1, k=3, pad=2 if loss_type == "curl" else 1)
+    return NetGraph(c_i, int(c_o), b.ch, b.nodes, pad_mode=r_p, act=act, divisor=4 ** levels)
 
 
-def _fluid_trunk(levels, c_i, c_h, *, act, r_p, use_symm, repeats, f, factor):
+def _fluid_trunk(levels, c_i, c_h, *, r_p, use_symm, repeats, f, factor):
     """The multi-resolution trunk NewFluidNet and FluidNet share (reference pytorch_networks_convae.py:1315-1337 and
     :1642-1658): level l = the input feature map average-pooled l times, `repeats` FluidLayers, bicubic back to the input
     size; concat of the levels with the raw inputs.  The reference re-pools the feature map from scratch for every level; the
-    values are identical to pooling the previous level once more, which is what the graph does.  Returns (channels, nodes,
-    tensor id of the concat, new-tensor function).  Any c_h with learned padding (the run list's configurations, pinned by
-    the reference goldens); with fixed padding c_h must stay a multiple of 8."""
+    values are identical to pooling the previous level once more, which is what the graph does.  Returns (builder, tensor id
+    of the concat).  Any c_h with learned padding (the run list's configurations, pinned by the reference goldens); with fixed
+    padding c_h must stay a multiple of 8."""
     learned = r_p == "learned"
     if c_h % 8 and not learned:
         raise NotImplementedError("the HIP path of NewFluidNet / FluidNet with fixed padding needs c_h to be a multiple of 8 "
                                   "(r_p='learned' takes any c_h)")
-    ch: Dict[int, int] = {0: c_i}
-    nodes = []
-    nid = [0]
-
-    def new(c):
-        nid[0] += 1
-        ch[nid[0]] = c
-        return nid[0]
-
-    def fluid(prefix, src, c_out):
-        out = new(c_out)
-        node = ConvNode(prefix + "layers.0.", [src], out, c_out, f, f // 2, _sym_h(c_out) if use_symm else 0,
-                        L.POST_GN_ACT, prefix + "layers.1.", _groups(c_out), learned=learned)
-        nodes.append(node)
-        return node
-
-    x_in = fluid("conv.0.", 0, c_h).out
+    b = _Builder(c_i, f, use_symm, learned)
+    x_in = b.fluid("conv.0.", [0], c_h).out
     pooled = x_in
     outs = []
     for l in range(levels):
         if l > 0:
-            p = new(c_h)
-            nodes.append(PoolNode(pooled, p, factor))
+            p = b.new(c_h)
+            b.nodes.append(PoolNode(pooled, p, factor))
             pooled = p
         cur = pooled
         for r in range(repeats):
-            cur = fluid(f"convs.{l}.{r}.", cur, c_h).out
+            cur = b.fluid(f"convs.{l}.{r}.", [cur], c_h).out
         if l > 0:
-            up = new(c_h)
-            nodes.append(UpNode(cur, up, like=x_in))
+            up = b.new(c_h)
+            b.nodes.append(UpNode(cur, up, like=x_in))
             cur = up
         outs.append(cur)
-    cat = new(c_h * levels + c_i)
-    nodes.append(CatNode(outs + [0], cat))
-    return ch, nodes, cat, new
+    cat = b.new(c_h * levels + c_i)
+    b.nodes.append(CatNode(outs + [0], cat))
+    return b, cat
+
+
+def _fluid_head(b, cat, c_h, c_o, *, act, r_p, **first) -> NetGraph:
+    """conv.1 (+ gn.0 + act), conv.2 (+ act), conv.3 on the trunk's concat: 3 x 3 convs with fixed padding, k = f
+    BoundaryLearnedConvolution2D layers with learned padding (reference :1296-1313).  first: what conv.1 alone takes."""
+    k = b.f if b.learned else 3
+    o = b.conv("conv.1.", [cat], c_h, L.POST_GN_ACT, "gn.0.", int(c_h / 4), k=k, **first).out
+    o2 = b.conv("conv.2.", [o], c_h, L.POST_ACT, None, 1, k=k).out
+    b.conv("conv.3.", [o2], c_o, L.POST_NONE, None, 1, k=k)
+    c_i = b.ch[0]
+    return NetGraph(c_i, c_o, b.ch, b.nodes, subtract_mean=True, pad_mode="zeros" if b.learned else r_p, act=act, divisor=1)
 
 
 def newfluidnet_graph(levels, c_i, c_h, c_o, *, act, r_p, use_symm, repeats, f, factor=2) -> NetGraph:
     """Layer wiring of NewFluidNet.__init__/forward (reference pytorch_networks_convae.py:1215-1346): the shared trunk
-    (_fluid_trunk), then a 3 x 3 head (k = f with learned padding)."""
-    learned = r_p == "learned"          # every conv a BoundaryLearnedConvolution2D; the head then uses k = f (reference :1296-1313)
-    ch, nodes, cat, new = _fluid_trunk(levels, c_i, c_h, act=act, r_p=r_p, use_symm=use_symm, repeats=repeats, f=f,
-                                       factor=factor)
-    hk = f if learned else 3
-
-    def hsym(c):
-        return (_sym_h(c) if use_symm else 0) if learned else 0
-
-    o = new(c_h)
-    nodes.append(ConvNode("conv.1.", [cat], o, c_h, hk, hk // 2, hsym(c_h), L.POST_GN_ACT, "gn.0.", int(c_h / 4), learned=learned))
-    o2 = new(c_h)
-    nodes.append(ConvNode("conv.2.", [o], o2, c_h, hk, hk // 2, hsym(c_h), L.POST_ACT, None, 1, learned=learned))
-    o3 = new(c_o)
-    nodes.append(ConvNode("conv.3.", [o2], o3, c_o, hk, hk // 2, hsym(c_o), L.POST_NONE, None, 1, learned=learned))
-    return NetGraph(c_i, c_o, ch, nodes, subtract_mean=True, pad_mode="zeros" if learned else r_p, act=act, divisor=1)
+    (_fluid_trunk), then the head (_fluid_head)."""
+    b, cat = _fluid_trunk(levels, c_i, c_h, r_p=r_p, use_symm=use_symm, repeats=repeats, f=f, factor=factor)
+    return _fluid_head(b, cat, c_h, c_o, act=act, r_p=r_p)
 
 
 def fluidnet_graph(levels, c_i, c_h, c_o, *, act, r_p, use_symm, repeats, f, factor=2) -> NetGraph:
@@ -315,24 +299,8 @@ def fluidnet_graph(levels, c_i, c_h, c_o, *, act, r_p, use_symm, repeats, f, fac
     k = f BoundaryLearnedConvolution2D called with bc_x = bc_y = 2 (:1660), conv.2 / conv.3 plain learned convs.  Fixed
     padding: conv.1 is the constructor's 3 x 3 conv with padding (2, 2), conv.2 / conv.3 3 x 3 with padding 1 (the reference's
     forward passes bc_x / bc_y to that nn.Conv2d and fails)."""
-    learned = r_p == "learned"
-    ch, nodes, cat, new = _fluid_trunk(levels, c_i, c_h, act=act, r_p=r_p, use_symm=use_symm, repeats=repeats, f=f,
-                                       factor=factor)
-    if learned:
-        def head(name, src, c_out, post, gn_name, groups, bc):
-            o = new(c_out)
-            nodes.append(ConvNode(name, [src], o, c_out, f, f // 2, _sym_h(c_out) if use_symm else 0, post, gn_name, groups,
-                                  learned=True, bc_x=bc, bc_y=bc))
-            return o
-    else:
-        def head(name, src, c_out, post, gn_name, groups, bc):
-            o = new(c_out)
-            nodes.append(ConvNode(name, [src], o, c_out, 3, 1 + (bc - 1), 0, post, gn_name, groups))
-            return o
-    o = head("conv.1.", cat, c_h, L.POST_GN_ACT, "gn.0.", int(c_h / 4), 2)
-    o2 = head("conv.2.", o, c_h, L.POST_ACT, None, 1, 1)
-    head("conv.3.", o2, c_o, L.POST_NONE, None, 1, 1)
-    return NetGraph(c_i, c_o, ch, nodes, subtract_mean=True, pad_mode="zeros" if learned else r_p, act=act, divisor=1)
+    b, cat = _fluid_trunk(levels, c_i, c_h, r_p=r_p, use_symm=use_symm, repeats=repeats, f=f, factor=factor)
+    return _fluid_head(b, cat, c_h, c_o, act=act, r_p=r_p, **(dict(bc_x=2, bc_y=2) if b.learned else dict(pad=2)))
 
 
 def single_layer_graph(c_in, c_out, k, pad, pad_mode, sym_h, post, act, groups, gn: bool, learned: bool = False,
@@ -560,8 +528,7 @@ class Engine:
         size, grad, convs = shape_walk(g, N, H, W, self.precision)
         T: Dict[int, _T] = {tid: _T(C=c, H=size[tid][0], W=size[tid][1], requires_grad=grad[tid])
                             for tid, c in g.channels.items()}
-        mode = L.PAD_MODES[g.pad_mode]
-        self.mode = mode
+        self.mode = L.PAD_MODES[g.pad_mode]
         f32 = dict(dtype=torch.float32, device=device)
         self.plan = []
         max_dy = 0
@@ -612,81 +579,12 @@ class Engine:
                     off += c
                 self.plan.append(dict(node=node, gather=gather))
                 continue
-            srcs = [T[t] for t in node.srcs]
             o = T[node.out]
-            h, w, ho, wo = srcs[0].H, srcs[0].W, o.H, o.W
-            if node.learned:
-                e = self._plan_learned(node, convs[i], srcs[0], o, cb8, cb8g, f32)
-                if node.pool > 1:
-                    T[node.pooled].buf = cb8(node.c_out, T[node.pooled].H, T[node.pooled].W)
-                self.plan.append(e)
-                max_dy = max(max_dy, N * e["coutp"] * ho * wo)
-                continue
-            d, dd, final_f32 = convs[i].d, convs[i].dd, convs[i].final_f32
-            tiles = L.call("mc_conv_tiles", C.byref(d))
-            if tiles <= 0:
-                raise L.MantleHipError(f"unsupported convolution configuration for {node.name} "
-                                       f"({self.precision}, c_in={srcs[0].C}+{d.c_in1}, c_out={node.c_out}, k={node.k})")
-            coutp = ((node.c_out + 7) // 8) * 8
-            need_dgrad = convs[i].dgrad
-            e = dict(node=node, desc=d, ddesc=dd, tiles=tiles, coutp=coutp,
-                     Y=(torch.empty((N, (node.c_out + 7) // 8, ho, wo, 8), dtype=torch.float32, device=device)
-                        if final_f32 else cb8(node.c_out, ho, wo)),
-                     part=torch.empty((N, tiles, coutp, 2), **f32),
-                     bank=torch.empty(L.call("mc_packed_weight_bytes", C.byref(d), 0), dtype=torch.uint8, device=device),
-                     need_dgrad=need_dgrad)
-            fusable = all(c.kind == "up" or (c.kind == "conv" and not c.learned) for c in cons[node.out])
-            o.fused = bool((self.fuse & 1) and node.post != L.POST_NONE and fusable and (cons[node.out] or node.pool > 1)
-                           and ho * wo <= self.fuse_maxpix)
-            if o.fused:
-                o.raw, o.act = e["Y"], L.ACTS[g.act]
-            elif node.post != L.POST_NONE:
-                o.buf = cb8(node.c_out, ho, wo)
-            else:
-                o.buf = e["Y"]
-            self.prod[node.out] = e
-            if node.post == L.POST_GN_ACT:
-                e["stats"] = torch.empty((N, node.groups, 2), **f32)
-                e["coef"] = torch.zeros((N, coutp, 4), **f32)       # (scale, shift, mean, rstd); padded channels stay 0
-                if o.fused:
-                    o.coef = e["coef"]
-                blocks = L.call("mc_gn_bwd_blocks", ho, wo)
-                e["gblocks"] = blocks
-                e["gpart"] = torch.empty((N, blocks, coutp, 2), **f32)
-                e["m12"] = torch.empty((N, node.groups, 2), **f32)
-                # small layers: reduce + finalize + apply of the GroupNorm backward in one launch (mc_gn_act_bwd_small)
-                if ho * wo <= self.gn_small_pix and (node.c_out // node.groups) in (1, 2, 4, 8):
-                    e["pc"] = torch.empty((N, coutp, 2), **f32)
+            plan = self._plan_learned if node.learned else self._plan_conv
+            e = plan(node, convs[i], [T[t] for t in node.srcs], o, cb8, cb8g, f32)
             if node.pool > 1:
                 T[node.pooled].buf = cb8(node.c_out, T[node.pooled].H, T[node.pooled].W)
-            if need_dgrad:
-                e["dbank"] = torch.empty(L.call("mc_packed_weight_bytes", C.byref(d), 1), dtype=torch.uint8,
-                                         device=device)
-                hp, wp = h + 2 * node.pad, w + 2 * node.pad
-                e["dxp"] = [cb8g(s.C, hp, wp) for s in srcs]
-                # GroupNorm-backward reduction fused into this launch's epilogue: the source is the full-resolution output
-                # of a conv + (GN) + act layer and this conv is its only consumer
-                pe = self.prod.get(node.srcs[0])
-                dz_here = bool(self.fuse & 2) and h * w <= self.fuse_maxpix
-                if (not dz_here and self.fuse_dz_rr and g.act == "gelu"
-                        and L.load().mc_conv_kernel_name(C.byref(dd)).decode().startswith("k_conv_rr")):
-                    dz_here = True
-                if (dz_here and len(srcs) == 1 and pe is not None and pe["node"].post != L.POST_NONE
-                        and not pe["node"].learned and len(cons[node.srcs[0]]) == 1 and pe["node"].pool == 1
-                        ):
-                    dtiles = L.call("mc_conv_tiles", C.byref(dd))
-                    fblocks = L.call("mc_fold_blocks", h, w, node.pad, mode)
-                    e["epi"] = pe
-                    pe["dz_tiles"], pe["dz_blocks"] = dtiles, dtiles + fblocks
-                    pe["dz_part"] = torch.empty((N, dtiles + fblocks, pe["coutp"], 2), **f32)
-                    if "m12" not in pe and pe["node"].post == L.POST_GN_ACT:
-                        pe["m12"] = torch.empty((N, pe["node"].groups, 2), **f32)
-                    if (pe["node"].post == L.POST_GN_ACT and pe["dz_blocks"] > 256
-                            and (pe["node"].c_out // pe["node"].groups) in (1, 2, 4, 8)):
-                        pe["dz_pc"] = torch.empty((N, pe["coutp"], 2), **f32)
-            max_dy = max(max_dy, N * coutp * ho * wo)
-            # per-layer filter-gradient partial slabs: all layers are combined by ONE batched launch at the end of backward
-            e["wpart"] = torch.empty(L.call("mc_wgrad_partial_bytes", C.byref(d)), dtype=torch.uint8, device=device)
+            max_dy = max(max_dy, N * e["coutp"] * o.H * o.W)
             self.plan.append(e)
         self.T = T
         # one output-gradient buffer for every layer: backward is one stream, so a layer's filter- and input-gradient
@@ -707,12 +605,83 @@ class Engine:
         self.gmean = torch.empty((N, g.c_out), **f32) if g.subtract_mean else None
         self.shape = (N, H, W, str(device))
 
+    def _plan_gn(self, e, node, o, f32):
+        """GroupNorm statistics and the buffers of the stand-alone backward reduction, for either kind of conv layer."""
+        N = self.N
+        e["stats"] = torch.empty((N, node.groups, 2), **f32)
+        e["gblocks"] = L.call("mc_gn_bwd_blocks", o.H, o.W)
+        e["gpart"] = torch.empty((N, e["gblocks"], e["coutp"], 2), **f32)
+        e["m12"] = torch.empty((N, node.groups, 2), **f32)
+
+    def _plan_conv(self, node, shape, srcs, o, cb8, cb8g, f32):
+        """A convolution with fixed padding over one or two sources: its buffers, whether its activated output is materialised
+        (o.fused) and whether its input-gradient launch carries the source layer's GroupNorm-backward reduction (e["epi"])."""
+        g, N, device = self.g, self.N, self.device
+        h, w, ho, wo = srcs[0].H, srcs[0].W, o.H, o.W
+        d, dd, final_f32 = shape.d, shape.dd, shape.final_f32
+        tiles = L.call("mc_conv_tiles", C.byref(d))
+        if tiles <= 0:
+            raise L.MantleHipError(f"unsupported convolution configuration for {node.name} "
+                                   f"({self.precision}, c_in={srcs[0].C}+{d.c_in1}, c_out={node.c_out}, k={node.k})")
+        coutp = ((node.c_out + 7) // 8) * 8
+        e = dict(node=node, desc=d, ddesc=dd, tiles=tiles, coutp=coutp,
+                 Y=(torch.empty((N, (node.c_out + 7) // 8, ho, wo, 8), dtype=torch.float32, device=device)
+                    if final_f32 else cb8(node.c_out, ho, wo)),
+                 part=torch.empty((N, tiles, coutp, 2), **f32),
+                 bank=torch.empty(L.call("mc_packed_weight_bytes", C.byref(d), 0), dtype=torch.uint8, device=device),
+                 need_dgrad=shape.dgrad)
+        cons = self.cons[node.out]
+        fusable = all(c.kind == "up" or (c.kind == "conv" and not c.learned) for c in cons)
+        o.fused = bool((self.fuse & 1) and node.post != L.POST_NONE and fusable and (cons or node.pool > 1)
+                       and ho * wo <= self.fuse_maxpix)
+        if o.fused:
+            o.raw, o.act = e["Y"], L.ACTS[g.act]
+        elif node.post != L.POST_NONE:
+            o.buf = cb8(node.c_out, ho, wo)
+        else:
+            o.buf = e["Y"]
+        self.prod[node.out] = e
+        if node.post == L.POST_GN_ACT:
+            self._plan_gn(e, node, o, f32)
+            e["coef"] = torch.zeros((N, coutp, 4), **f32)       # (scale, shift, mean, rstd); padded channels stay 0
+            if o.fused:
+                o.coef = e["coef"]
+            # small layers: reduce + finalize + apply of the GroupNorm backward in one launch (mc_gn_act_bwd_small)
+            if ho * wo <= self.gn_small_pix and (node.c_out // node.groups) in (1, 2, 4, 8):
+                e["pc"] = torch.empty((N, coutp, 2), **f32)
+        if shape.dgrad:
+            e["dbank"] = torch.empty(L.call("mc_packed_weight_bytes", C.byref(d), 1), dtype=torch.uint8, device=device)
+            hp, wp = h + 2 * node.pad, w + 2 * node.pad
+            e["dxp"] = [cb8g(s.C, hp, wp) for s in srcs]
+            # GroupNorm-backward reduction fused into this launch's epilogue: the source is the full-resolution output
+            # of a conv + (GN) + act layer and this conv is its only consumer
+            pe = self.prod.get(node.srcs[0])
+            dz_here = bool(self.fuse & 2) and h * w <= self.fuse_maxpix
+            if (not dz_here and self.fuse_dz_rr and g.act == "gelu"
+                    and L.load().mc_conv_kernel_name(C.byref(dd)).decode().startswith("k_conv_rr")):
+                dz_here = True
+            if (dz_here and len(srcs) == 1 and pe is not None and pe["node"].post != L.POST_NONE
+                    and not pe["node"].learned and len(self.cons[node.srcs[0]]) == 1 and pe["node"].pool == 1):
+                dtiles = L.call("mc_conv_tiles", C.byref(dd))
+                fblocks = L.call("mc_fold_blocks", h, w, node.pad, self.mode)
+                e["epi"] = pe
+                pe["dz_tiles"], pe["dz_blocks"] = dtiles, dtiles + fblocks
+                pe["dz_part"] = torch.empty((N, dtiles + fblocks, pe["coutp"], 2), **f32)
+                if "m12" not in pe and pe["node"].post == L.POST_GN_ACT:
+                    pe["m12"] = torch.empty((N, pe["node"].groups, 2), **f32)
+                if (pe["node"].post == L.POST_GN_ACT and pe["dz_blocks"] > 256
+                        and (pe["node"].c_out // pe["node"].groups) in (1, 2, 4, 8)):
+                    pe["dz_pc"] = torch.empty((N, pe["coutp"], 2), **f32)
+        # per-layer filter-gradient partial slabs: all layers are combined by ONE batched launch at the end of backward
+        e["wpart"] = torch.empty(L.call("mc_wgrad_partial_bytes", C.byref(d)), dtype=torch.uint8, device=device)
+        return e
+
     # -------------------------------------------------------------- learned padding (BoundaryLearnedConvolution2D)
-    def _plan_learned(self, node, shape, s, o, cb8, cb8g, f32):
+    def _plan_learned(self, node, shape, srcs, o, cb8, cb8g, f32):
         """The main bank on the library's conv kernels, the frame of the eight border banks on the mc_learned_frame_* kernels,
         which read the input / the output gradient in place (reference pytorch_networks_convae.py:1022-1065).  The gradient
         w.r.t. the input needs no padded domain: the adjoint of a valid convolution is exactly input-sized."""
-        N, u8 = self.N, dict(dtype=torch.uint8, device=self.device)
+        (s,), N, u8 = srcs, self.N, dict(dtype=torch.uint8, device=self.device)
         reg, d, dd = shape.banks["conv"]                          # the valid convolution on the whole input
         ld = L.LearnedDesc(N, s.H, s.W, s.C, node.c_out, node.k, node.bc_x, node.bc_y, self.mc_dtype, node.sym_h)
         if L.call("mc_learned_validate", C.byref(ld)) != 0 or L.call("mc_conv_tiles", C.byref(d)) <= 0:
@@ -741,10 +710,7 @@ class Engine:
                  lws_bytes=L.call("mc_learned_wgrad_workspace_bytes", C.byref(ld)))
         o.buf = cb8(node.c_out, o.H, o.W) if node.post != L.POST_NONE else e["Y"]
         if node.post == L.POST_GN_ACT:
-            e["stats"] = torch.empty((N, node.groups, 2), **f32)
-            e["gblocks"] = L.call("mc_gn_bwd_blocks", o.H, o.W)
-            e["gpart"] = torch.empty((N, e["gblocks"], coutp, 2), **f32)
-            e["m12"] = torch.empty((N, node.groups, 2), **f32)
+            self._plan_gn(e, node, o, f32)
         return e
 
     def _learned_forward(self, e, src, params, need_part, st):
@@ -775,6 +741,13 @@ class Engine:
             L.call("mc_conv2d", C.byref(e["ddesc"]), L.ptr(e["dR"]), None, L.ptr(e["dbank"]), None, L.ptr(e["dxl"]), None, None, st)
             L.call("mc_learned_frame_dgrad", C.byref(e["ldesc"]), L.ptr(dY), L.ptr(e["ldbank"]), L.ptr(e["dxl"]), st)
             src.gsrcs.append(L.GradSrc(L.ptr(e["dxl"]), L.GSRC_PLAIN, 0, 0, 1, src.H, src.W))
+
+    def input_grad(self):
+        """input_grad_cb8() as an NCHW f32 tensor (what the autograd bridge returns for the input)."""
+        dxl, s = self.input_grad_cb8(), self.T[0]
+        dx = torch.empty((self.N, s.C, s.H, s.W), dtype=torch.float32, device=dxl.device)
+        L.call("mc_unpack_nchw", L.ptr(dxl), self.N, s.C, s.H, s.W, 0, None, self.mc_gdtype, L.ptr(dx), L.stream())
+        return dx
 
     def input_grad_cb8(self):
         """d(loss)/d(input) of a graph built with input_grad=True, as backward left it: CB8 [N][C8][H][W][8] in the gradient

@@ -15,7 +15,8 @@ DEFAULT_PRECISION = os.environ.get("MANTLE_PRECISION", "fp32")
 
 
 class _NetFunction(torch.autograd.Function):
-    """y = engine.forward(x); backward runs the HIP backward and hands parameter gradients to autograd."""
+    """y = engine.forward(x); backward runs the HIP backward and hands parameter gradients to autograd (and the input's, for
+    a graph built with input_grad)."""
 
     @staticmethod
     def forward(ctx, mod, x, *plist):
@@ -40,9 +41,11 @@ class _NetFunction(torch.autograd.Function):
         for n, s in zip(names, sizes):
             grads[n] = flat[off:off + s].view(ctx.params[n].shape)
             off += s
-        mod.engine().backward(gout, ctx.params, grads)
+        eng = mod.engine()
+        eng.backward(gout, ctx.params, grads)
         outs = [grads[n] if dt == torch.float32 else grads[n].to(dt) for n, dt in zip(names, ctx.dtypes)]
-        return (None, None, *outs)
+        dx = eng.input_grad() if (mod._graph.input_grad and ctx.needs_input_grad[1]) else None
+        return (None, dx, *outs)
 
 
 class HipNetMixin:

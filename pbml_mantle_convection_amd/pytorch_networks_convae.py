@@ -16,7 +16,7 @@ import torch.nn.functional as F
 import torch.optim as optim
 
 from . import _lib as L
-from .engine import convae_graph, fluidnet_graph, newfluidnet_graph, single_layer_graph, unet_graph
+from .engine import convae_graph, fluid_groups, fluid_sym_h, fluidnet_graph, newfluidnet_graph, single_layer_graph, unet_graph
 from .hipnet import HipNetMixin
 from .learned_padding import BoundaryLearnedConvolution2D   # noqa: F401  (reference :802-1065)
 from .symmetric_layers_torch import SymmetricConv2d
@@ -159,7 +159,7 @@ class FluidLayer(nn.Module, HipNetMixin):
         self.r_p = "constant" if r_p == "zeros" else r_p
         self.act_fn = act_fn
         self.layers = nn.ModuleList()
-        h_s = int(c_o / 4) if c_o > 4 else int(c_o / 2)
+        h_s = fluid_sym_h(c_o)
         if r_p == "learned":
             self.layers.append(BoundaryLearnedConvolution2D(c_i, c_o, k=f, use_symm=use_symm))      # reference :760-763
         elif use_symm:
@@ -168,9 +168,9 @@ class FluidLayer(nn.Module, HipNetMixin):
         else:
             self.layers.append(nn.Conv2d(c_i, c_o, kernel_size=f, padding="same", dilation=dilation,
                                          padding_mode=r_p))
-        self.layers.append(torch.nn.GroupNorm(int(c_o / min(4, c_o)), c_o))
+        self.layers.append(torch.nn.GroupNorm(fluid_groups(c_o), c_o))
         self._init_hipnet(single_layer_graph(c_i, c_o, f, f // 2, "zeros" if r_p == "learned" else r_p,
-                                             h_s if use_symm else 0, L.POST_GN_ACT, act_fn, int(c_o / min(4, c_o)), gn=True,
+                                             h_s if use_symm else 0, L.POST_GN_ACT, act_fn, fluid_groups(c_o), gn=True,
                                              learned=(r_p == "learned")))
 
     def forward(self, inputs, bc_x=1, bc_y=1):

@@ -304,3 +304,63 @@ def test_launch_budget_module(call_counts):
     torch.cuda.synchronize()
     _check_budget(call_counts)
     assert x.grad is not None and all(p.grad is not None for p in m.parameters())
+
+
+@pytest.mark.parametrize("precision", list(PREC))
+@pytest.mark.parametrize("case", ["deepest_8x31", "tiny_6x7", "k3_head_4x5"])
+def test_module_on_engine(case, precision):
+    """The stand-alone BoundaryLearnedConvolution2D is a one-node graph behind the autograd bridge: y, x.grad and the ten
+    parameter gradients against the f64 oracle in every precision; bit-equal to an Engine driven by hand on the module's
+    graph; bit-reproduced after the module re-planned for another shape; one in-flight forward per module."""
+    from pbml_mantle_convection_amd import engine as E
+    from pbml_mantle_convection_amd.pytorch_networks_convae import BoundaryLearnedConvolution2D
+    c_i, c_o, k, symm, _, _, h, w = CASES[case]
+    _, tx, tg = PREC[precision]
+    o = oracle(case, None if precision == "fp32" else tx)
+    m = BoundaryLearnedConvolution2D(c_i, c_o, k, use_symm=symm)
+    m.load_state_dict({n: t.float() for n, t in o["sd"].items()})
+    m = m.to(DEV).set_precision(precision)
+    x = o["x"].float().to(DEV).requires_grad_(True)
+    ct = o["ct"].float().to(DEV)
+
+    def run():
+        x.grad = None
+        m.zero_grad()
+        y = m(x)
+        y.backward(ct)
+        torch.cuda.synchronize()
+        return [y.detach().clone(), x.grad.clone(), {n: p.grad.clone() for n, p in m.named_parameters()}]
+
+    y, dx, grads = first = run()
+    a, r = tol("y", precision, o["y"], stored=tx)
+    assert_close(y.cpu().double(), o["y"], a, r, f"{case} {precision} module y")
+    a, r = tol("dx", precision, o["dx"], stored=tg)
+    assert_close(dx.cpu().double(), o["dx"], a, r, f"{case} {precision} module dx")
+    assert len(grads) == 10
+    for n, gr in grads.items():
+        assert gr.shape == o["sd"][n].shape
+        a, r = tol("param", precision, o["grads"][n])
+        assert_close(gr.cpu().double(), o["grads"][n], a, r, f"{case} {precision} module grad {n}")
+    # the same code gives the same bits: an engine on the module's graph, driven by hand
+    eng = E.Engine(m._graph, precision)
+    params = {n: p.detach() for n, p in m.named_parameters()}
+    egrads = {n: torch.zeros_like(p) for n, p in params.items()}
+    ey = eng.forward(x.detach(), params)
+    eng.backward(ct, params, egrads)
+    torch.cuda.synchronize()
+    assert torch.equal(y, ey)
+    assert torch.equal(dx.cpu().double(), from_cb8(eng.input_grad_cb8(), c_i))
+    for n in grads:
+        assert torch.equal(grads[n], egrads[n]), n
+    # another shape re-plans the module's engine; back at the first shape the results are reproduced bit for bit
+    x2 = torch.randn((N, c_i, h + 3, w + 3), generator=torch.Generator().manual_seed(9)).to(DEV)
+    assert m(x2).shape == (N, c_o, h + 3, w + 3)
+    y_b, dx_b, grads_b = run()
+    assert torch.equal(y_b, y) and torch.equal(dx_b, dx)
+    for n in grads:
+        assert torch.equal(grads_b[n], grads[n]), n
+    # a later forward overwrites the device activations of an earlier one
+    stale = m(x)
+    m(x)
+    with pytest.raises(RuntimeError, match="one in-flight forward"):
+        stale.backward(ct)
