@@ -32,15 +32,15 @@ def rel_l2(a, b):
 
 
 @pytest.mark.parametrize("ci,co,k,mode,h,hw", [
-    (16, 16, 5, "reflect", 4, (37, 45)),      # NT=1 config, one K-chunk, ragged tiles
+    (16, 16, 5, "reflect", 4, (37, 45)),      # one output tile: row-reuse kernel (16 x 64 tiles), one K-chunk, ragged tiles
     (11, 16, 5, "replicate", 4, (33, 40)),    # padded input channels
     (48, 16, 5, "reflect", 4, (20, 35)),      # three K-chunks
-    (16, 32, 5, "zeros", 8, (18, 37)),        # NT=2 config
-    (32, 64, 5, "reflect", 16, (17, 19)),     # NT=4 config
+    (16, 32, 5, "zeros", 8, (18, 37)),        # NT=2 config, 8-row tiles (at most 40 output rows)
+    (32, 64, 5, "reflect", 16, (17, 19)),     # NT=4 config, 8-row tiles
     (64, 128, 5, "reflect", 32, (9, 12)),     # two N-groups of NT=4
     (16, 4, 5, "reflect", 0, (21, 33)),       # plain conv, 4 output channels
     (8, 16, 3, "reflect", 4, (19, 23)),       # 3x3
-    (16, 48, 3, "zeros", 0, (10, 20)),        # 3 N-tiles -> NT=1 x 3 groups
+    (16, 48, 3, "zeros", 0, (10, 20)),        # 3 output tiles: row-reuse kernel, 3 work-group columns
 ])
 def test_bf16_conv_forward_and_filter_gradient(ci, co, k, mode, h, hw):
     from pbml_mantle_convection_amd.symmetric_layers_torch import SymmetricConv2d
@@ -205,11 +205,11 @@ def test_training_steps_bf16_vs_golden(golden, tag):
 @pytest.mark.parametrize("ci0,ci1,co,k,h,hw", [
     (16, 0, 16, 5, 4, (21, 30)),      # N = 16
     (16, 32, 16, 5, 4, (18, 19)),     # concat sources: N = 48 -> 3 groups, split output
-    (32, 64, 32, 5, 8, (12, 17)),     # N = 96 (NT = 2 x 3 groups), K over 32 channels (2 chunks)
+    (32, 64, 32, 5, 8, (12, 17)),     # N = 96 (NT = 2 x 3 groups, 8-row tiles), K over 32 channels (2 chunks)
     (64, 128, 64, 5, 16, (9, 10)),    # N = 192 (NT = 4 x 3 groups)
     (8, 0, 4, 3, 0, (14, 15)),        # tiny channel counts, 3x3
-    (32, 0, 32, 5, 8, (31, 33)),      # padded domain of 35 rows: the 12-row tile (3 x 12 instead of 3 x 16), NT = 2
-    (64, 128, 64, 5, 16, (17, 18)),   # 21 rows: 12-row tiles with NT = 4, three N-groups
+    (32, 0, 32, 5, 8, (31, 33)),      # padded domain of 35 rows: 8-row tiles (5 x 8; at most 40 rows), NT = 2
+    (64, 128, 64, 5, 16, (17, 18)),   # 21 rows: 8-row tiles (3 x 8) with NT = 4, three N-groups
 ])
 def test_input_gradient_kernel_direct(dtype_name, ci0, ci1, co, k, h, hw):
     """mc_conv2d in input-gradient mode (padded domain, rotated/transposed bank, split outputs) against
