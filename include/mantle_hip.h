@@ -503,6 +503,35 @@ int mc_adnet_step(const float* u, const float* v, int64_t uv_stride, const float
                   const float* raq_field, const float* raq_scalar, const float* xc, const float* yc, int32_t n, int32_t h,
                   int32_t w, float cn_max, int32_t compute_dt, float* dt_io, uint32_t* ws, float* T_next, void* stream);
 
+/* ---- spectral layer (SpectralConv2d, pytorch_networks_convae.py:571-635) as a truncated DFT ---- */
+/* Only the modes K1 = (0, 1, 2, 3, h-4, h-3, h-2, h-1) x K2 = (0, 1, 2, 3) of rfft2 survive the layer; mode index
+ * m = k1i * 4 + k2.  Twiddle tables (f32, built on the host in f64 from integer-reduced arguments):
+ * rowtw [h][5][2] = (cos, sin)(2 pi (k y mod h) / h) for k = 0..4, coltw [w][4][2] likewise for k2 = 0..3.
+ * Both streaming kernels run one block per (slot, channel block, sample): slot = a chunk of rows x a 256-column strip.
+ * mc_spectral_slots: slots per sample (<= 64) for an h x w grid, or -1 when h < 8 or w < 8 (the reference's two corner
+ * blocks would overlap or touch the Nyquist column) or the grid needs more than 64 slots of 128 rows.  No atomics. */
+int32_t mc_spectral_slots(int32_t h, int32_t w);
+/* A(t): x CB8 [n][c8][h][w][8] of the dtype code's type (MC_F32 f32, MC_BF16 bf16, MC_MIX16 f16; a gradient tensor of
+ * the mixed mode is passed as MC_BF16) -> per-slot partial mode sums part [n][slots][c8*8][8][4][2] f32. */
+int mc_spectral_analyze(const void* x, int32_t n, int32_t c, int32_t h, int32_t w, int32_t dtype, const float* rowtw,
+                        const float* coltw, float* part, void* stream);
+/* S(C): coef [n][c8*8][8][4][2] f32 -> y CB8 of the dtype code's type, lanes past c exactly zero.  gn_part != NULL: also
+ * the GroupNorm partials (sum, sum of squares) per channel of the f32 values before the store rounding,
+ * [n][slots][c8*8][2] (the layout mc_gn_finalize_coef reads with tiles = slots). */
+int mc_spectral_synthesize(const float* coef, int32_t n, int32_t c, int32_t h, int32_t w, int32_t dtype, const float* rowtw,
+                           const float* coltw, void* y, float* gn_part, void* stream);
+/* Mode space, forward: xhat [n][ci8*8][8][4][2] = the slots of part in slot order (kept for the backward pass);
+ * coef [n][co8*8][8][4][2] = gamma * sum_i xhat[n][i] Wt[i][o], gamma[k2] = (1, 2, 2, 2) / hw, lanes past c_out zero.
+ * w1 / w2: the parameters weights1 / weights2, [c_in][c_out][4][4] interleaved (re, im) f32. */
+int mc_spectral_mix_fwd(const float* part, int32_t n, int32_t slots, int32_t c_in, int32_t c_out, int32_t hw, const float* w1,
+                        const float* w2, float* xhat, float* coef, void* stream);
+/* Mode space, backward: part = A(dy) [n][slots][co8*8][8][4][2]; gbuf [n][co8*8][8][4][2] workspace (G = gamma * the
+ * slots in order); dw1 / dw2 ACCUMULATE sum_n conj(xhat[n][i]) G[n][o], the samples in order ((d/dRe, d/dIm) interleaved,
+ * what torch keeps in .grad of a complex parameter); dxcoef (may be NULL) [n][ci8*8][8][4][2] = sum_o conj(Wt[i][o]) G[n][o],
+ * the coefficients mc_spectral_synthesize turns into the input gradient. */
+int mc_spectral_mix_bwd(const float* part, int32_t n, int32_t slots, int32_t c_in, int32_t c_out, int32_t hw, const float* w1,
+                        const float* w2, const float* xhat, float* gbuf, float* dw1, float* dw2, float* dxcoef, void* stream);
+
 /* ---- optimizer (torch.optim.Adam, multigpu.py:761-763) --------------------------------------- */
 /* One fused multi-tensor step over flat f32 buffers; grad_scale folds the 1/world_size of the
  * data-parallel average; lr is read from device memory so a captured graph can be replayed

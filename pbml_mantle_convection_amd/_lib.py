@@ -151,13 +151,19 @@ SIGNATURES = {
     "mc_momentum_residual": (C.c_int, [_LD, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mc_momentum_adjoint": (C.c_int, [_LD, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mc_loss_finalize": (C.c_int, [_LD, _vp, _vp, _vp]),
+    "mc_spectral_slots": (_i32, [_i32, _i32]),
+    "mc_spectral_analyze": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "mc_spectral_synthesize": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "mc_spectral_mix_fwd": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "mc_spectral_mix_bwd": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mc_adam_step_flat": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _f32, _f32, _f32, _f32, _f32, _vp, _vp]),
 }
 
 # entry points whose return value is a quantity, not a status code
 VALUE_RETURNING = {"mc_version", "mc_strerror", "mc_conv_kernel_name", "mc_packed_weight_bytes", "mc_conv_bank_read_extent", "mc_conv_tiles",
                    "mc_wgrad_partial_bytes", "mc_gn_bwd_blocks",
-                   "mc_learned_validate", "mc_learned_bank_bytes", "mc_learned_wgrad_workspace_bytes", "mc_fold_blocks", "mc_loss_fused_blocks"}
+                   "mc_learned_validate", "mc_learned_bank_bytes", "mc_learned_wgrad_workspace_bytes", "mc_fold_blocks", "mc_loss_fused_blocks",
+                   "mc_spectral_slots"}
 
 _lib = None
 

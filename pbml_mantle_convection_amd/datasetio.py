@@ -463,8 +463,8 @@ class SyntheticMantleDataset(Dataset):
             # ConvAE plumbing config (CFG-1): T (+ two parameter maps) -> (u, v, p)
             self.x = torch.stack([self.x[:, 7], self.x[:, 3], self.x[:, 4]], 1) if (c_i or 3) == 3 else self.x[:, :c_i]
             self.y = self.y[:, :3]
-        elif network in ("fluidnet", "ifluidnet"):
-            # NewADDataset-shaped items of the FluidNet branch: 7 input channels, truth (u, v[, p]) without T
+        elif "fluidnet" in network:
+            # (fluidnet / ifluidnet / newfluidnet, the reference's `"fluidnet" in self.net`) NewADDataset-shaped items of the FluidNet branch: 7 input channels, truth (u, v[, p]) without T
             self.x = self.x[:, :(c_i or 7)]
             self.y = self.y[:, :3] if p_pred else self.y[:, :2]
 
@@ -472,6 +472,6 @@ class SyntheticMantleDataset(Dataset):
         return self.x.shape[0]
 
     def __getitem__(self, i):
-        if self.network in ("convae", "fluidnet", "ifluidnet"):
+        if self.network == "convae" or "fluidnet" in self.network:
             return self.x[i], self.y[i], torch.tensor(0.0), self.scaler[i]
         return self.x[i], self.y[i], self.scaler[i], self.paras[i].view(3, 1, 1), self.yc.view(1, *self.yc.shape)

@@ -53,6 +53,7 @@ class ConvNode:
     bc_y: int = 1              # border strips so that the output grows (Unet's first layer, reference :1995)
     sym_v: int = 0             # y-mirrored filters / filters mirrored about both axes (SymmetricConv2d symmetry 'v' / 'hv';
     sym_hv: int = 0            # FluidLayer never sets them, reference :755-757)
+    spectral: bool = False     # SpectralConv2d (reference :571-635): name + {weights1, weights2}, no bias; k = pad = sym = 0
 
 
 @dataclass
@@ -131,8 +132,16 @@ class _Builder:
         self.nodes.append(node)
         return node
 
-    def fluid(self, prefix, srcs, c_out, **kw):
-        """A FluidLayer: conv + GroupNorm + activation."""
+    def fluid(self, prefix, srcs, c_out, spectral=False, **kw):
+        """A FluidLayer: conv + GroupNorm + activation; spectral: a SpectralFluidLayer (reference :638-699), whose GroupNorm
+        has int(c_o / 4) groups."""
+        if spectral:
+            if c_out < 4:
+                raise ValueError(f"{prefix}: a spectral layer needs c_o >= 4 (GroupNorm has int(c_o / 4) groups), got {c_out}")
+            node = ConvNode(prefix + "layers.0.", list(srcs), self.new(c_out), c_out, 0, 0, 0, L.POST_GN_ACT, prefix + "layers.1.",
+                            int(c_out / 4), spectral=True, **kw)
+            self.nodes.append(node)
+            return node
         return self.conv(prefix + "layers.0.", srcs, c_out, L.POST_GN_ACT, prefix + "layers.1.", fluid_groups(c_out), symm=True, **kw)
 
 
@@ -241,19 +250,20 @@ def convae_graph(levels, c_i, c_h, c_o, *, act, r_p, use_symm, repeats, f, loss_
     return NetGraph(c_i, int(c_o), b.ch, b.nodes, pad_mode=r_p, act=act, divisor=4 ** levels)
 
 
-def _fluid_trunk(levels, c_i, c_h, *, r_p, use_symm, repeats, f, factor):
+def _fluid_trunk(levels, c_i, c_h, *, r_p, use_symm, repeats, f, factor, spectral=False):
     """The multi-resolution trunk NewFluidNet and FluidNet share (reference pytorch_networks_convae.py:1315-1337 and
     :1642-1658): level l = the input feature map average-pooled l times, `repeats` FluidLayers, bicubic back to the input
     size; concat of the levels with the raw inputs.  The reference re-pools the feature map from scratch for every level; the
     values are identical to pooling the previous level once more, which is what the graph does.  Returns (builder, tensor id
     of the concat).  Any c_h with learned padding (the run list's configurations, pinned by the reference goldens); with fixed
-    padding c_h must stay a multiple of 8."""
+    padding c_h must stay a multiple of 8.  spectral: every FluidLayer of the trunk is a SpectralFluidLayer (:1211-1254,
+    :1535-1570); the heads stay what they are."""
     learned = r_p == "learned"
     if c_h % 8 and not learned:
         raise NotImplementedError("the HIP path of NewFluidNet / FluidNet with fixed padding needs c_h to be a multiple of 8 "
                                   "(r_p='learned' takes any c_h)")
     b = _Builder(c_i, f, use_symm, learned)
-    x_in = b.fluid("conv.0.", [0], c_h).out
+    x_in = b.fluid("conv.0.", [0], c_h, spectral=spectral).out
     pooled = x_in
     outs = []
     for l in range(levels):
@@ -263,7 +273,7 @@ def _fluid_trunk(levels, c_i, c_h, *, r_p, use_symm, repeats, f, factor):
             pooled = p
         cur = pooled
         for r in range(repeats):
-            cur = b.fluid(f"convs.{l}.{r}.", [cur], c_h).out
+            cur = b.fluid(f"convs.{l}.{r}.", [cur], c_h, spectral=spectral).out
         if l > 0:
             up = b.new(c_h)
             b.nodes.append(UpNode(cur, up, like=x_in))
@@ -285,31 +295,36 @@ def _fluid_head(b, cat, c_h, c_o, *, act, r_p, **first) -> NetGraph:
     return NetGraph(c_i, c_o, b.ch, b.nodes, subtract_mean=True, pad_mode="zeros" if b.learned else r_p, act=act, divisor=1)
 
 
-def newfluidnet_graph(levels, c_i, c_h, c_o, *, act, r_p, use_symm, repeats, f, factor=2) -> NetGraph:
+def newfluidnet_graph(levels, c_i, c_h, c_o, *, act, r_p, use_symm, repeats, f, factor=2, spectral=False) -> NetGraph:
     """Layer wiring of NewFluidNet.__init__/forward (reference pytorch_networks_convae.py:1215-1346): the shared trunk
     (_fluid_trunk), then the head (_fluid_head)."""
-    b, cat = _fluid_trunk(levels, c_i, c_h, r_p=r_p, use_symm=use_symm, repeats=repeats, f=f, factor=factor)
+    b, cat = _fluid_trunk(levels, c_i, c_h, r_p=r_p, use_symm=use_symm, repeats=repeats, f=f, factor=factor, spectral=spectral)
     return _fluid_head(b, cat, c_h, c_o, act=act, r_p=r_p)
 
 
-def fluidnet_graph(levels, c_i, c_h, c_o, *, act, r_p, use_symm, repeats, f, factor=2) -> NetGraph:
+def fluidnet_graph(levels, c_i, c_h, c_o, *, act, r_p, use_symm, repeats, f, factor=2, spectral=False) -> NetGraph:
     """Layer wiring of FluidNet.__init__/forward with loss_type 'curl' (reference pytorch_networks_convae.py:1581-1665): the
     trunk of NewFluidNet, then a head whose first conv grows the field by one pixel on every side, so that the output is
     (H + 2) x (W + 2) and the curl head's centred differences land on H x W (mc_curl_valid_*).  Learned padding: conv.1 is a
     k = f BoundaryLearnedConvolution2D called with bc_x = bc_y = 2 (:1660), conv.2 / conv.3 plain learned convs.  Fixed
     padding: conv.1 is the constructor's 3 x 3 conv with padding (2, 2), conv.2 / conv.3 3 x 3 with padding 1 (the reference's
     forward passes bc_x / bc_y to that nn.Conv2d and fails)."""
-    b, cat = _fluid_trunk(levels, c_i, c_h, r_p=r_p, use_symm=use_symm, repeats=repeats, f=f, factor=factor)
+    b, cat = _fluid_trunk(levels, c_i, c_h, r_p=r_p, use_symm=use_symm, repeats=repeats, f=f, factor=factor, spectral=spectral)
     return _fluid_head(b, cat, c_h, c_o, act=act, r_p=r_p, **(dict(bc_x=2, bc_y=2) if b.learned else dict(pad=2)))
 
 
 def single_layer_graph(c_in, c_out, k, pad, pad_mode, sym_h, post, act, groups, gn: bool, learned: bool = False,
-                       sym_v: int = 0, sym_hv: int = 0, bc_x: int = 1, bc_y: int = 1, input_grad: bool = False) -> NetGraph:
+                       sym_v: int = 0, sym_hv: int = 0, bc_x: int = 1, bc_y: int = 1, input_grad: bool = False,
+                       spectral: bool = False) -> NetGraph:
     """One conv (+GN+act): SymmetricConv2d / FluidLayer / BoundaryLearnedConvolution2D (learned; bc_x, bc_y as in its forward)
-    used stand-alone.  input_grad (learned layers): backward leaves d(loss)/d(input) in Engine.input_grad_cb8()."""
-    if input_grad and not learned:
-        raise NotImplementedError("input_grad is implemented for learned-padding layers")
+    / SpectralConv2d / SpectralFluidLayer (spectral; k, pad, sym are ignored) used stand-alone.  input_grad (learned and
+    spectral layers): backward leaves d(loss)/d(input) in Engine.input_grad_cb8()."""
+    if input_grad and not (learned or spectral):
+        raise NotImplementedError("input_grad is implemented for learned-padding and spectral layers")
     ch = {0: c_in, 1: c_out}
+    if spectral:
+        node = ConvNode("layers.0." if gn else "", [0], 1, c_out, 0, 0, 0, post, "layers.1." if gn else None, groups, spectral=True)
+        return NetGraph(c_in, c_out, ch, [node], pad_mode="zeros", act=act, input_grad=input_grad)
     node = ConvNode("layers.0." if gn else "", [0], 1, c_out, k, pad, sym_h, post, "layers.1." if gn else None, groups,
                     learned=learned, sym_v=sym_v, sym_hv=sym_hv, bc_x=bc_x, bc_y=bc_y)
     return NetGraph(c_in, c_out, ch, [node], pad_mode=pad_mode, act=act, input_grad=input_grad)
@@ -388,7 +403,14 @@ def shape_walk(g: NetGraph, N: int, H: int, W: int, precision: str):
         cs = [g.channels[t] for t in node.srcs]
         dgrad = any(grad[t] for t in node.srcs)
         k = node.k
-        if node.learned:
+        if node.spectral:
+            assert len(cs) == 1, "a spectral layer takes one source tensor"
+            if h < 8 or w < 8:
+                raise ValueError(f"{node.name}: a spectral layer needs H >= 8 and W >= 8 (its two 4 x 4 mode blocks would overlap "
+                                 f"or touch the Nyquist column), got {h}x{w}")
+            ho, wo = h, w
+            convs[i] = ConvShape(dgrad)
+        elif node.learned:
             assert len(cs) == 1, "learned padding takes one source tensor"
             _, _, ho, wo, regs = learned_regions(h, w, k, node.bc_x, node.bc_y)
             if any(sy < 0 or sx < 0 or sh < k or sw < k for sy, sx, sh, sw, _, _ in regs.values()):
@@ -414,6 +436,8 @@ def iter_conv_descs(g: NetGraph, N: int, H: int, W: int, precision: str):
     N x H x W, from the shape walk Engine.configure plans on (host-side checks: tests/test_abi_and_host.py compares every
     launch's bank reach with the bank's size)."""
     for i, c in shape_walk(g, N, H, W, precision)[2].items():
+        if g.nodes[i].spectral:              # no convolution launch: a truncated DFT
+            continue
         if c.banks is None:
             yield g.nodes[i].name, c.d, c.dd
         else:
@@ -453,6 +477,19 @@ def bicubic_tables(n_in: int, n_out: int):
             tw.append(lists[i][oo])
         start[i + 1] = len(tj)
     return (idx, w.astype(np.float32), start, np.asarray(tj, np.int32), np.asarray(tw, np.float32))
+
+
+# ------------------------------------------------------------------------------------------------
+# twiddle tables of the spectral layers, built in f64 from integer-reduced arguments
+# ------------------------------------------------------------------------------------------------
+def spectral_tables(H: int, W: int):
+    """(rowtw [H][5][2], coltw [W][4][2]) f32: (cos, sin)(2 pi ((k h) mod H) / H) for |k1| = k = 0..4 and
+    (cos, sin)(2 pi ((k2 w) mod W) / W) for k2 = 0..3."""
+    def tab(n, ks):
+        r = (np.arange(n, dtype=np.int64)[:, None] * np.arange(ks, dtype=np.int64)[None, :]) % n
+        a = 2.0 * np.pi * r.astype(np.float64) / n
+        return np.stack([np.cos(a), np.sin(a)], -1).astype(np.float32)
+    return tab(H, 5), tab(W, 4)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -580,7 +617,7 @@ class Engine:
                 self.plan.append(dict(node=node, gather=gather))
                 continue
             o = T[node.out]
-            plan = self._plan_learned if node.learned else self._plan_conv
+            plan = self._plan_spectral if node.spectral else self._plan_learned if node.learned else self._plan_conv
             e = plan(node, convs[i], [T[t] for t in node.srcs], o, cb8, cb8g, f32)
             if node.pool > 1:
                 T[node.pooled].buf = cb8(node.c_out, T[node.pooled].H, T[node.pooled].W)
@@ -590,8 +627,9 @@ class Engine:
         # one output-gradient buffer for every layer: backward is one stream, so a layer's filter- and input-gradient
         # launches have read it before the next layer down writes its own
         self.dY = torch.empty(max_dy, dtype=self.g_dtype, device=device)
-        self.convs = [e for e in self.plan if e["node"].kind == "conv" and not e["node"].learned]
+        self.convs = [e for e in self.plan if e["node"].kind == "conv" and not e["node"].learned and not e["node"].spectral]
         self.learned = [e for e in self.plan if e["node"].kind == "conv" and e["node"].learned]
+        self.spectral = [e for e in self.plan if e["node"].kind == "conv" and e["node"].spectral]
         # one filter-gradient workspace for the frames of every learned layer (backward is one stream)
         self.lws = torch.empty(max([e["lws_bytes"] for e in self.learned] + [0]), dtype=torch.uint8, device=device)
         last = self.plan[-1]
@@ -631,7 +669,7 @@ class Engine:
                  bank=torch.empty(L.call("mc_packed_weight_bytes", C.byref(d), 0), dtype=torch.uint8, device=device),
                  need_dgrad=shape.dgrad)
         cons = self.cons[node.out]
-        fusable = all(c.kind == "up" or (c.kind == "conv" and not c.learned) for c in cons)
+        fusable = all(c.kind == "up" or (c.kind == "conv" and not c.learned and not c.spectral) for c in cons)
         o.fused = bool((self.fuse & 1) and node.post != L.POST_NONE and fusable and (cons or node.pool > 1)
                        and ho * wo <= self.fuse_maxpix)
         if o.fused:
@@ -661,7 +699,7 @@ class Engine:
                     and L.load().mc_conv_kernel_name(C.byref(dd)).decode().startswith("k_conv_rr")):
                 dz_here = True
             if (dz_here and len(srcs) == 1 and pe is not None and pe["node"].post != L.POST_NONE
-                    and not pe["node"].learned and len(self.cons[node.srcs[0]]) == 1 and pe["node"].pool == 1):
+                    and not pe["node"].learned and not pe["node"].spectral and len(self.cons[node.srcs[0]]) == 1 and pe["node"].pool == 1):
                 dtiles = L.call("mc_conv_tiles", C.byref(dd))
                 fblocks = L.call("mc_fold_blocks", h, w, node.pad, self.mode)
                 e["epi"] = pe
@@ -742,6 +780,63 @@ class Engine:
             L.call("mc_learned_frame_dgrad", C.byref(e["ldesc"]), L.ptr(dY), L.ptr(e["ldbank"]), L.ptr(e["dxl"]), st)
             src.gsrcs.append(L.GradSrc(L.ptr(e["dxl"]), L.GSRC_PLAIN, 0, 0, 1, src.H, src.W))
 
+    # -------------------------------------------------------------- spectral layers (SpectralConv2d)
+    def _plan_spectral(self, node, shape, srcs, o, cb8, cb8g, f32):
+        """A truncated DFT (csrc/spectral.hip): analysis of the materialised input, channel mixing in mode space, synthesis into
+        the raw output Y with the GroupNorm partials.  The GroupNorm / activation / pooling launches after it are the generic
+        ones; its input gradient is the input-sized buffer dxl, as for a learned-padding layer."""
+        (s,), N = srcs, self.N
+        slots = L.call("mc_spectral_slots", s.H, s.W)
+        if slots <= 0:
+            raise L.MantleHipError(f"unsupported spectral layer {node.name}: input {s.H}x{s.W}")
+        cinp, coutp = ((s.C + 7) // 8) * 8, ((node.c_out + 7) // 8) * 8
+        cmax = max(cinp, coutp)
+        need_dgrad = s.requires_grad
+        e = dict(node=node, tiles=slots, coutp=coutp, Y=cb8(node.c_out, o.H, o.W), part=torch.empty((N, slots, coutp, 2), **f32),
+                 tabs=self._spectral_table(s.H, s.W), need_dgrad=need_dgrad,
+                 apart=torch.empty((N, slots, cmax, 32, 2), **f32),      # per-slot mode sums of the input / of dY
+                 xhat=torch.empty((N, cinp, 32, 2), **f32),              # modes of the input, kept for the backward pass
+                 mcoef=torch.empty((N, cmax, 32, 2), **f32),             # coefficients of the output / of the input gradient
+                 gbuf=torch.empty((N, coutp, 32, 2), **f32),
+                 dxl=cb8g(s.C, s.H, s.W) if need_dgrad else None)
+        o.buf = cb8(node.c_out, o.H, o.W) if node.post != L.POST_NONE else e["Y"]
+        if node.post == L.POST_GN_ACT:
+            self._plan_gn(e, node, o, f32)
+        return e
+
+    def _spectral_table(self, H, W):
+        key = ("spectral", H, W)
+        if key not in self._tables:
+            self._tables[key] = tuple(torch.from_numpy(a).to(self.device) for a in spectral_tables(H, W))
+        return self._tables[key]
+
+    def _spectral_forward(self, e, src, params, need_part, st):
+        node, N = e["node"], self.N
+        w1, w2 = self._param(params, node.name + "weights1"), self._param(params, node.name + "weights2")
+        rowtw, coltw = e["tabs"]
+        L.call("mc_spectral_analyze", L.ptr(src.buf), N, src.C, src.H, src.W, self.mc_dtype, L.ptr(rowtw), L.ptr(coltw),
+               L.ptr(e["apart"]), st)
+        L.call("mc_spectral_mix_fwd", L.ptr(e["apart"]), N, e["tiles"], src.C, node.c_out, src.H * src.W, L.ptr(w1), L.ptr(w2),
+               L.ptr(e["xhat"]), L.ptr(e["mcoef"]), st)
+        L.call("mc_spectral_synthesize", L.ptr(e["mcoef"]), N, node.c_out, src.H, src.W, self.mc_dtype, L.ptr(rowtw), L.ptr(coltw),
+               L.ptr(e["Y"]), L.ptr(e["part"]) if need_part else None, st)
+
+    def _spectral_backward(self, e, src, dY, params, grads, st):
+        """dY -> its modes -> the two weight gradients (accumulated, samples in order) and the coefficients of the input
+        gradient -> dxl."""
+        node, N = e["node"], self.N
+        w1, w2 = self._param(params, node.name + "weights1"), self._param(params, node.name + "weights2")
+        rowtw, coltw = e["tabs"]
+        L.call("mc_spectral_analyze", L.ptr(dY), N, node.c_out, src.H, src.W, self.mc_gdtype, L.ptr(rowtw), L.ptr(coltw),
+               L.ptr(e["apart"]), st)
+        L.call("mc_spectral_mix_bwd", L.ptr(e["apart"]), N, e["tiles"], src.C, node.c_out, src.H * src.W, L.ptr(w1), L.ptr(w2),
+               L.ptr(e["xhat"]), L.ptr(e["gbuf"]), L.ptr(grads[node.name + "weights1"]), L.ptr(grads[node.name + "weights2"]),
+               L.ptr(e["mcoef"]) if e["need_dgrad"] else None, st)
+        if e["need_dgrad"]:
+            L.call("mc_spectral_synthesize", L.ptr(e["mcoef"]), N, src.C, src.H, src.W, self.mc_gdtype, L.ptr(rowtw), L.ptr(coltw),
+                   L.ptr(e["dxl"]), None, st)
+            src.gsrcs.append(L.GradSrc(L.ptr(e["dxl"]), L.GSRC_PLAIN, 0, 0, 1, src.H, src.W))
+
     def input_grad(self):
         """input_grad_cb8() as an NCHW f32 tensor (what the autograd bridge returns for the input)."""
         dxl, s = self.input_grad_cb8(), self.T[0]
@@ -751,7 +846,7 @@ class Engine:
 
     def input_grad_cb8(self):
         """d(loss)/d(input) of a graph built with input_grad=True, as backward left it: CB8 [N][C8][H][W][8] in the gradient
-        type (the first node must be a learned-padding layer reading the input)."""
+        type (the first node must be a learned-padding or spectral layer reading the input)."""
         e = self.plan[0]
         if not self.g.input_grad or not e["node"].kind == "conv" or e.get("dxl") is None:
             raise RuntimeError("this graph produces no input gradient")
@@ -814,8 +909,8 @@ class Engine:
                     L.call("mc_bicubic_fwd", L.ptr(s.buf), N, s.C, s.H, s.W, o.H, o.W, L.ptr(iy), L.ptr(wy), L.ptr(ix),
                            L.ptr(wx), self.mc_dtype, L.ptr(o.buf), st)
                 continue
-            d = e["desc"]
-            if not node.learned:
+            d = e.get("desc")
+            if not node.learned and not node.spectral:
                 w = self._param(params, node.name + "weight")
                 b = self._param(params, node.name + "bias")
             srcs = [T[i] for i in node.srcs]
@@ -826,6 +921,8 @@ class Engine:
             beta = self._param(params, node.gn_name + "bias") if node.gn_name else None
             if node.learned:
                 self._learned_forward(e, srcs[0], params, need_part, st)
+            elif node.spectral:
+                self._spectral_forward(e, srcs[0], params, need_part, st)
             else:
                 self._probe_begin()
                 x0, x1, pro = self._sources(srcs)
@@ -833,7 +930,7 @@ class Engine:
                        L.ptr(e["part"]) if need_part else None, None, st)
                 self._probe_end(d, "fwd " + node.name)
             small = (node.post == L.POST_GN_ACT and "pc" in e and not o.fused and node.pool in (1, 2)
-                     and not node.learned and (self.fuse == 0 or self.fuse_dz_rr) and "dz_blocks" not in e)
+                     and not node.learned and not node.spectral and (self.fuse == 0 or self.fuse_dz_rr) and "dz_blocks" not in e)
             if small:
                 # statistics + activation (+ pooling) of a small layer in one launch
                 pooled = T[node.pooled].buf if node.pool > 1 else None
@@ -967,7 +1064,7 @@ class Engine:
                            L.ptr(e["dsrc"]), st)
                 s.gsrcs.append(L.GradSrc(L.ptr(e["dsrc"]), L.GSRC_PLAIN, 0, 0, 1, s.H, s.W))
                 continue
-            d = e["desc"]
+            d = e.get("desc")
             o = T[node.out]
             srcs = [T[i] for i in node.srcs]
             if node.post != L.POST_NONE and "dz" in e:
@@ -1020,6 +1117,9 @@ class Engine:
                            self.mc_dtype, g0, g1, L.ptr(dY), st)
             if node.learned:
                 self._learned_backward(e, srcs[0], dY, params, grads, st)
+                continue
+            if node.spectral:
+                self._spectral_backward(e, srcs[0], dY, params, grads, st)
                 continue
             x0, x1, pro = self._sources(srcs)
             L.call("mc_conv2d_wgrad_fused", C.byref(d), x0, x1, pro, L.ptr(dY), L.ptr(e["wpart"]), st)
@@ -1190,7 +1290,7 @@ class Engine:
         for e in self.plan:
             if e["node"].kind != "conv":
                 continue
-            if e["node"].learned:
+            if e["node"].learned or e["node"].spectral:      # (a spectral layer reads its input once and writes its output once)
                 src, o = self.T[e["node"].srcs[0]], self.T[e["node"].out]
                 tot += src.C * src.H * src.W + o.C * o.H * o.W
                 continue

@@ -36,14 +36,17 @@ class _NetFunction(torch.autograd.Function):
                                "forward of the same module (one in-flight forward per module)")
         names = mod._pnames
         sizes = [ctx.params[n].numel() for n in names]
-        flat = torch.zeros(sum(sizes), dtype=torch.float32, device=gout.device)
-        grads, off = {}, 0
-        for n, s in zip(names, sizes):
-            grads[n] = flat[off:off + s].view(ctx.params[n].shape)
-            off += s
+        offs, off = [], 0
+        for s in sizes:                          # 16-byte aligned slices (a complex view needs an even offset)
+            offs.append(off)
+            off = (off + s + 3) // 4 * 4
+        flat = torch.zeros(off, dtype=torch.float32, device=gout.device)
+        grads = {n: flat[o:o + s].view(ctx.params[n].shape) for n, o, s in zip(names, offs, sizes)}
         eng = mod.engine()
         eng.backward(gout, ctx.params, grads)
-        outs = [grads[n] if dt == torch.float32 else grads[n].to(dt) for n, dt in zip(names, ctx.dtypes)]
+        # (a complex parameter's gradient is the interleaved (d/dRe, d/dIm) pair the engine accumulated)
+        outs = [torch.view_as_complex(grads[n]).to(dt) if dt.is_complex else grads[n] if dt == torch.float32 else grads[n].to(dt)
+                for n, dt in zip(names, ctx.dtypes)]
         dx = eng.input_grad() if (mod._graph.input_grad and ctx.needs_input_grad[1]) else None
         return (None, dx, *outs)
 
@@ -83,7 +86,9 @@ class HipNetMixin:
         out = {}
         for n, p in zip(self._pnames, plist):
             d = p.detach()
-            if d.dtype != torch.float32:
+            if d.is_complex():               # the engine reads a complex parameter as interleaved (re, im) f32: [..., 2]
+                d = torch.view_as_real(d.to(torch.complex64).contiguous())
+            elif d.dtype != torch.float32:
                 d = d.float()
             out[n] = d.contiguous()
         return out
@@ -100,29 +105,41 @@ class HipNetMixin:
 class FlatParams:
     """One flat f32 device buffer for all parameters and one for their gradients; the module's
     nn.Parameters become views, so reference-style code (state_dict, torch optimizers) keeps
-    working while the fused Adam kernel and the single RCCL all-reduce see flat memory."""
+    working while the fused Adam kernel and the single RCCL all-reduce see flat memory.
+
+    A complex parameter (the spectral layers' complex64 weights) takes 2 numel f32 slots, interleaved (re, im): p.data and
+    p.grad are torch.view_as_complex views of the flat buffers (slices start on multiples of 4 floats, so the views are
+    aligned), views() hands the engine the real [..., 2] view, and Adam on the interleaved floats is what torch.optim.Adam
+    does to a complex tensor."""
 
     def __init__(self, module: nn.Module, device):
         named = [(n, p) for n, p in module.named_parameters()]
         self.names = [n for n, _ in named]
-        self.shapes = [tuple(p.shape) for _, p in named]
+        self.complex = [p.is_complex() for _, p in named]
+        self.shapes = [tuple(p.shape) + ((2,) if p.is_complex() else ()) for _, p in named]      # as f32 views
         self.offsets = []
         total = 0
         for _, p in named:
             total = (total + 3) // 4 * 4      # 16-byte aligned slices
             self.offsets.append(total)
-            total += p.numel()
+            total += p.numel() * (2 if p.is_complex() else 1)
         total = (total + 3) // 4 * 4
         self.numel = total
         self.param = torch.zeros(total, dtype=torch.float32, device=device)
         self.grad = torch.zeros(total, dtype=torch.float32, device=device)
         self.module = module
         with torch.no_grad():
-            for (n, p), off, shp in zip(named, self.offsets, self.shapes):
-                view = self.param[off:off + p.numel()].view(shp)
-                view.copy_(p.detach().to(device=device, dtype=torch.float32))
+            for (n, p), off, shp, cplx in zip(named, self.offsets, self.shapes, self.complex):
+                size = int(torch.Size(shp).numel())
+                view = self.param[off:off + size].view(shp)
+                gview = self.grad[off:off + size].view(shp)
+                if cplx:
+                    view.copy_(torch.view_as_real(p.detach().to(device=device, dtype=torch.complex64).contiguous()))
+                    view, gview = torch.view_as_complex(view), torch.view_as_complex(gview)
+                else:
+                    view.copy_(p.detach().to(device=device, dtype=torch.float32))
                 p.data = view
-                p.grad = self.grad[off:off + p.numel()].view(shp)
+                p.grad = gview
 
         self._views = {}
 

@@ -505,7 +505,8 @@ def load_train_objs(rank, world_size, nn_dir, data_dir, levels, c_i, c_h, c_o, a
     if restart:
         epoch, start_lr, milestones = parse_restart_log(nn_dir, milestones)
         sd = torch.load(nn_dir + str(epoch) + "_fluidnet_uvp.pt", map_location="cpu", weights_only=True)
-        model_uvp.load_state_dict({k: v.float() for k, v in sd.items()})
+        # (f32 masters; the spectral layers' complex weights are complex64)
+        model_uvp.load_state_dict({k: v.to(torch.complex64) if v.is_complex() else v.float() for k, v in sd.items()})
         epoch += 1
         print("Restarting from epoch, lr, milestones")
         print(epoch, start_lr, milestones)

@@ -2,7 +2,8 @@
 (reference pytorch_networks_convae.py; ConvAE from .ipynb_checkpoints/pycold-checkpoint.py:989-1115),
 executed by the HIP engine on MI355X.
 
-Only the modules on the training hot path are provided (FluidLayer, Unet, ConvAE, NewFluidNet, FluidNet) plus the
+Only the modules on the training hot path are provided (FluidLayer, SpectralConv2d, SpectralFluidLayer, Unet, ConvAE,
+NewFluidNet, FluidNet) plus the
 small field helpers the reference exports from this module.  Everything numeric inside
 forward()/backward() runs in libmantle_hip kernels; there is no CPU path.
 """
@@ -135,7 +136,7 @@ def pad_uvp(u, v, p=None):
 # --------------------------------------------------------------------------------------------------
 # FluidLayer (reference :702-799): conv -> GroupNorm -> activation -> dropout(p)
 # --------------------------------------------------------------------------------------------------
-def _check_common(act_fn, r_p, dilation, drop_rate=0.0, spectral_conv=False, blurr=False):
+def _check_common(act_fn, r_p, dilation, drop_rate=0.0, spectral_conv=False, blurr=False, spectral_ok=False):
     if act_fn not in _SUPPORTED_ACTS:
         raise NotImplementedError(f"act_fn={act_fn!r}: supported on the HIP path: {_SUPPORTED_ACTS} "
                                   "('sine' is undefined in the reference itself)")
@@ -145,8 +146,8 @@ def _check_common(act_fn, r_p, dilation, drop_rate=0.0, spectral_conv=False, blu
         raise NotImplementedError("dilation != 1 is not implemented on the HIP path")
     if drop_rate not in (0, 0.0):
         raise NotImplementedError("dropout with p > 0 is not implemented on the HIP path (reference default 0)")
-    if spectral_conv:
-        raise NotImplementedError("spectral_conv is out of scope (FFT path)")
+    if spectral_conv and not spectral_ok:
+        raise NotImplementedError("spectral_conv is built for NewFluidNet and FluidNet (the Unet's spectral layers are not)")
     if blurr:
         raise NotImplementedError("blurr is out of scope")
 
@@ -177,6 +178,47 @@ class FluidLayer(nn.Module, HipNetMixin):
         if self.r_p == "learned" and (bc_x != 1 or bc_y != 1):
             raise NotImplementedError("a stand-alone FluidLayer runs the learned padding with bc_x = bc_y = 1 (inside the Unet "
                                       "graph the first layer's bc_x = 4 is part of the graph)")
+        return self._run_graph(inputs)
+
+
+# --------------------------------------------------------------------------------------------------
+# SpectralConv2d / SpectralFluidLayer (reference :571-699): rfft2 -> 4 x 4-mode channel mixing in two corner blocks -> irfft2
+# (-> GroupNorm -> activation), executed as a truncated DFT (csrc/spectral.hip)
+# --------------------------------------------------------------------------------------------------
+class SpectralConv2d(nn.Module, HipNetMixin):
+    """modes1 / modes2 are accepted and ignored: the reference hard-codes 4 (:588-591).  The weights are complex64 (the
+    project keeps f32 masters; the reference's are cdouble)."""
+
+    def __init__(self, in_channels, out_channels, modes1=4, modes2=4):
+        super().__init__()
+        self.in_channels, self.out_channels = in_channels, out_channels
+        self.modes1 = self.modes2 = 4
+        self.scale = 1 / (in_channels * out_channels)
+        self.weights1 = nn.Parameter(self.scale * torch.rand(in_channels, out_channels, 4, 4, dtype=torch.complex64))
+        self.weights2 = nn.Parameter(self.scale * torch.rand(in_channels, out_channels, 4, 4, dtype=torch.complex64))
+        self._init_hipnet(single_layer_graph(in_channels, out_channels, 0, 0, "zeros", 0, L.POST_NONE, "gelu", 1, gn=False,
+                                             spectral=True, input_grad=True))
+
+    def forward(self, x):
+        return self._run_graph(x)
+
+
+class SpectralFluidLayer(nn.Module, HipNetMixin):
+    def __init__(self, c_i: int, c_o: int, act_fn: str = "selu", r_p="zeros", use_symm=False, dilation=1, f=3):
+        super().__init__()
+        if act_fn not in _SUPPORTED_ACTS:
+            raise NotImplementedError(f"act_fn={act_fn!r}: supported on the HIP path: {_SUPPORTED_ACTS}")
+        if c_o < 4:
+            raise ValueError(f"a spectral layer needs c_o >= 4 (GroupNorm has int(c_o / 4) groups), got {c_o}")
+        self.r_p = "constant" if r_p == "zeros" else r_p      # (kept for the reference's attribute; the layer pads nothing)
+        self.act_fn = act_fn
+        self.layers = nn.ModuleList()
+        self.layers.append(SpectralConv2d(c_i, c_o, c_o, c_o))
+        self.layers.append(torch.nn.GroupNorm(int(c_o / 4), c_o))
+        self._init_hipnet(single_layer_graph(c_i, c_o, 0, 0, "zeros", 0, L.POST_GN_ACT, act_fn, int(c_o / 4), gn=True,
+                                             spectral=True, input_grad=True))
+
+    def forward(self, inputs):
         return self._run_graph(inputs)
 
 
@@ -323,16 +365,18 @@ class NewFluidNet(nn.Module, HipNetMixin):
                  loss_type="mae", use_symm=False, dilation=1, a_bound=4.0, use_cosine=False, repeats=3, use_skip=False,
                  f=3, p_pred=True, spectral_conv=False, blurr=False, drop_rate=0.0, factor=2):
         super().__init__()
-        _check_common(act_fn, r_p, dilation, drop_rate, spectral_conv, blurr)
+        _check_common(act_fn, r_p, dilation, drop_rate, spectral_conv, blurr, spectral_ok=True)
         self.levels, self.loss_type, self.a_bound = levels, loss_type, a_bound
         self.use_cosine, self.repeats, self.use_skip, self.p_pred = use_cosine, repeats, use_skip, p_pred
         self.c_h, self.c_i, self.c_o = c_h, c_i, c_o
         self.blurrer = None
         self.r_p = "constant" if r_p == "zeros" else r_p
         graph = newfluidnet_graph(levels, c_i, c_h, c_o, act=act_fn, r_p=r_p, use_symm=use_symm, repeats=repeats, f=f,
-                                  factor=factor)
+                                  factor=factor, spectral=spectral_conv)
 
         def fl(cin, cout):
+            if spectral_conv:                                                  # reference :1211-1254
+                return SpectralFluidLayer(cin, cout, act_fn, r_p, use_symm, dilation, f=f)
             return FluidLayer(cin, cout, act_fn, r_p, use_symm, dilation, f=f, drop_rate=drop_rate)
 
         # module tree in the reference's construction order (:1148-1313) so state_dict keys match
@@ -418,7 +462,7 @@ class FluidNet(nn.Module, HipNetMixin):
                  loss_type="mae", use_symm=False, dilation=1, a_bound=4.0, use_cosine=False, repeats=3, use_skip=False,
                  f=3, p_pred=True, spectral_conv=False, blurr=False, drop_rate=0.0, factor=2):
         super().__init__()
-        _check_common(act_fn, r_p, dilation, drop_rate, spectral_conv, blurr)
+        _check_common(act_fn, r_p, dilation, drop_rate, spectral_conv, blurr, spectral_ok=True)
         if loss_type in ("mae", "mass"):
             raise NotImplementedError(f"FluidNet with loss_type={loss_type!r} fails in the reference (its forward skips conv.1, so "
                                       "GroupNorm sees c_h * levels + c_i channels); only 'curl' is built")
@@ -439,9 +483,11 @@ class FluidNet(nn.Module, HipNetMixin):
         self.r_p = "constant" if r_p == "zeros" else r_p
         self.act = {"selu": nn.SELU, "tanh": nn.Tanh, "elu": nn.ELU, "silu": nn.SiLU, "relu": nn.ReLU, "gelu": nn.GELU}[act_fn]()
         graph = fluidnet_graph(levels, c_i, c_h, c_o, act=act_fn, r_p=r_p, use_symm=use_symm, repeats=repeats, f=f,
-                               factor=factor)
+                               factor=factor, spectral=spectral_conv)
 
         def fl(cin, cout):
+            if spectral_conv:                                                  # reference :1535-1570
+                return SpectralFluidLayer(cin, cout, act_fn, r_p, use_symm, dilation, f=f)
             return FluidLayer(cin, cout, act_fn, r_p, use_symm, dilation, f=f, drop_rate=drop_rate)
 
         self.conv.append(fl(c_i, c_h))

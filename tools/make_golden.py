@@ -868,10 +868,119 @@ def g23():
         cfg=np.array([3, 10, 6, 2, 2, 5, 0, 0, 1, 1, R]), **_grad_samples(m))
 
 
+# ------------------------------------------------------------------ G24 spectral layers (-spectral 1)
+def _randomize_complex_(module, seed):
+    """fp32-representable random complex parameters (randomize_ fills real values only): the reference's scale of
+    1 / fan_in^0.5 per part instead of its 1 / (c_i c_o) rand, so that the second block and the imaginary parts matter."""
+    g = torch.Generator().manual_seed(seed)
+    with torch.no_grad():
+        for n, p in module.named_parameters():
+            if p.is_complex():
+                fan = p.shape[0] * 32
+                re, im = (torch.randn(p.shape, generator=g) / fan ** 0.5).float(), (torch.randn(p.shape, generator=g) / fan ** 0.5).float()
+                p.copy_(torch.complex(re, im).to(p.dtype))
+
+
+def _sd_c(module, prefix="sd/"):
+    """state_dict with complex entries kept complex (complex64: fp32-representable by construction)."""
+    return {prefix + k: (v.detach().to(torch.complex64) if v.is_complex() else v.detach().float())
+            for k, v in module.state_dict().items()}
+
+
+def g24():
+    # (a) two stand-alone SpectralFluidLayers: odd in both directions with ragged channel blocks; tanh, 12 channels = 3 groups
+    save = {}
+    for tag, (c_i, c_o, H, W, act) in {"a": (11, 16, 9, 11, "gelu"), "b": (6, 12, 16, 70, "tanh")}.items():
+        m = P.SpectralFluidLayer(c_i, c_o, act, "zeros", True, 1, f=5).double()
+        randomize_(m, 240)
+        _randomize_complex_(m, 241)
+        x = rnd((2, c_i, H, W), 242).requires_grad_(True)
+        y = m(x)
+        ct = rnd(y.shape, 243)
+        (y * ct).sum().backward()
+        save.update({f"{tag}/x": x.detach().float(), f"{tag}/y": y, f"{tag}/ct": ct.float(), f"{tag}/dx": x.grad,
+                     f"{tag}/meta": np.array([c_i, c_o, H, W]), f"{tag}/act": np.array(act)})
+        save.update(_sd_c(m, f"{tag}/sd/"))
+        save.update(grads_np(m, f"{tag}/grad/"))
+    npz("g24_spectral_layer", **save)
+    # (b) the deployed trunk's geometry, small: five levels 128 x 506 ... 8 x 31 (the minimum a spectral layer takes)
+    m = P.NewFluidNet(5, 7, 8, 3, CPU, "gelu", "zeros", "mae", use_symm=True, repeats=1, f=5, p_pred=True, spectral_conv=True).double()
+    randomize_(m, 244)
+    _randomize_complex_(m, 245)
+    x = torch.from_numpy(fields.unet_input(1, 128, 506, 246, c_i=7)).requires_grad_(True)
+    outs = m(x)
+    loss, save = 0.0, {}
+    for n, o in zip("uvp", outs):
+        # cotangents: random (a plain sum of the outputs has zero gradient: the head subtracts the spatial mean)
+        ct = rnd(o.shape, 247 + len(save))
+        loss = loss + (o * ct).sum()
+        save["out/" + n] = fields.strided_sample(o.detach().numpy(), 2003)
+    loss.backward()
+    sd = m.state_dict()
+    npz("g24_newfluidnet_spectral", cfg=np.array([5, 7, 8, 3, 1, 5, 1, 1]), **save, **_sd_c(m),
+        **{k_: (v.to(torch.complex64) if v.is_complex() else v.float()) for k_, v in grads_np(m).items()},
+        keys=np.array(list(sd.keys())), dtypes=np.array([str(v.dtype) for v in sd.values()]),
+        shapes=np.array([",".join(map(str, v.shape)) for v in sd.values()]), count=np.array(P.count_parameters(m)))
+    # (c) FluidNet with learned-padding heads and the curl head on a spectral trunk
+    m = P.FluidNet(2, 7, 8, 1, CPU, "gelu", "learned", "curl", use_symm=True, a_bound=10, repeats=1, f=5, p_pred=False,
+                   spectral_conv=True).double()
+    randomize_(m, 250)
+    _randomize_complex_(m, 251)
+    with torch.no_grad():
+        g_ = torch.Generator().manual_seed(252)
+        for n, p in m.named_parameters():
+            if n.endswith("learnable_bias"):
+                p.copy_((0.1 * torch.randn(p.shape, generator=g_)).float().double())
+    x = torch.from_numpy(fields.unet_input(1, 128, 506, 253, c_i=7)).requires_grad_(True)
+    u, v, p_ = m(x)
+    assert p_ is None
+    # cotangents: fields.smooth_field(1, 128, 506, 254 / 255) rounded to f32 (regenerated by the test, not stored)
+    ct = [torch.from_numpy(fields.smooth_field(1, 128, 506, 254 + i).astype(np.float32)).to(f64) for i in range(2)]
+    ((u * ct[0]).sum() + (v * ct[1]).sum()).backward()
+    sd = m.state_dict()
+    npz("g24_fluidnet_spectral", cfg=np.array([2, 7, 8, 1, 1, 5, 0, 1]), a_bound=np.array(10.0),
+        **{"out/" + n: fields.strided_sample(o.detach().numpy(), 2003) for n, o in (("u", u), ("v", v))}, **_sd_c(m),
+        **{k_: (v_.to(torch.complex64) if v_.is_complex() else v_.float()) for k_, v_ in grads_np(m).items()},
+        keys=np.array(list(sd.keys())), dtypes=np.array([str(v_.dtype) for v_ in sd.values()]),
+        shapes=np.array([",".join(map(str, v_.shape)) for v_ in sd.values()]), count=np.array(P.count_parameters(m)))
+    # (d) two complete steps zero_grad -> get_loss -> backward -> Adam (as g11) on a three-level spectral NewFluidNet: pins Adam
+    # on the complex parameters.  Loss flags of the deployed configuration (-l_sc 1, -l_de 0: what the CLI's run list and
+    # bench.py's newfluidnet workload use)
+    B, H, W = 2, 128, 506
+    m = P.NewFluidNet(3, 7, 8, 3, CPU, "gelu", "zeros", "mae", use_symm=True, repeats=1, f=5, p_pred=True, spectral_conv=True).double()
+    randomize_(m, 256)
+    _randomize_complex_(m, 257)
+    sd0 = _sd_c(m, "sd0/")
+    opt = torch.optim.Adam(m.parameters(), lr=1e-3, weight_decay=0.0)
+    ns = _trainer_ns(m, True, True, False, "mae")
+    ns.net = "newfluidnet"
+    inner = m
+
+    class Sq(torch.nn.Module):              # (p as [B, H, W] like u and v: the reference returns it un-squeezed)
+        def forward(self, x):
+            u, v, p = inner(x)
+            return u, v, p[:, 0]
+    ns.model_uvp = Sq()
+    losses = []
+    for step in range(2):
+        gVTp = torch.from_numpy(fields.unet_input(B, H, W, 2400 + step, c_i=7))
+        uvp = torch.from_numpy(np.stack([fields.smooth_field(B, H, W, 2410 + step), fields.smooth_field(B, H, W, 2420 + step),
+                                         fields.smooth_field(B, H, W, 2430 + step, amp=0.5)], 1))
+        opt.zero_grad()
+        out = G.Trainer.get_loss(ns, gVTp, uvp, None, None, None)
+        out[0].backward()
+        if step == 0:
+            g0 = {("grad0/" + k): p.grad.clone() for k, p in m.named_parameters()}
+        opt.step()
+        losses.append([float(o) for o in out])
+    npz("g24_train_newfluidnet_spectral", losses=np.array(losses), cfg=np.array([3, 7, 8, 3, 1, 5, 1, 1, 1, 0]), **sd0, **g0,
+        **{("sd2/" + k): v for k, v in m.state_dict().items()})
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     torch.set_num_threads(8)
     only = sys.argv[1:]
-    for fn in (g1, g2, g3, g4, g5, g6, g7, g8, g9, g10, g11, g12, g13, g14, g15, g16, g17, g18, g19, g20, g21, g22, g23):
+    for fn in (g1, g2, g3, g4, g5, g6, g7, g8, g9, g10, g11, g12, g13, g14, g15, g16, g17, g18, g19, g20, g21, g22, g23, g24):
         if not only or fn.__name__ in only:
             fn()
