@@ -260,6 +260,48 @@ int mc_gn_act_bwd_small(const void* y, int32_t n, int32_t c, int32_t h, int32_t 
                         const mc_grad_src* g1, void* dy, float* chan_sums, void* stream);
 int mc_gn_param_grads_batched(const float* const* chan_sums, const int32_t* n, const int32_t* c, float* const* dgamma,
                               float* const* dbeta, int32_t jobs, void* stream);
+/* ---- Dropout after the activation (nn.Dropout at the end of a FluidLayer, :753, :798) -------
+ * a_drop = a * m * s, element-wise.  An element is kept (m = 1) with probability keep16 / 65536, keep16 =
+ * clamp(round((1 - p) * 65536), 1, 65535), s = f32(65536 / keep16): the rate is quantised to 2^-16.  The mask is a pure
+ * function of (seed, step, layer, logical element) -- Philox4x32-10 with key (seed_lo, seed_hi) and counter (v_lo, v_hi,
+ * layer, step), v = ((n * c8 + cb) * h + y) * w + x the 64-bit index of the CB8 vector; channel j of the vector takes the
+ * 16-bit field (out[j >> 1] >> 16 (j & 1)) & 0xffff and is kept iff field < keep16 -- so it does not depend on dtype, kernel
+ * or launch shape, and the backward pass regenerates it instead of reading a stored mask.
+ * state: device uint32[4] = (seed_lo, seed_hi, step, 0), read by the kernels when they run (a replayed HIP graph sees the
+ * current step); mc_dropout_advance adds 1 to state[2] with a one-thread kernel on `stream`. */
+typedef struct {
+  const uint32_t* state;
+  uint32_t layer;
+  uint32_t keep16;
+} mc_dropout;
+int mc_dropout_advance(uint32_t* state, void* stream);
+/* The existing entry points with dropout: forward multiplies the f32 activation by m * s before the store rounding, backward
+ * multiplies the f32 sum of the gradient sources by m * s before act'.  Lanes past c stay zero.  pool must be 1
+ * (MC_EUNSUPPORTED otherwise: a dropout layer is never pooled in its own launch); drop == NULL or keep16 outside
+ * [1, 65535] is MC_EINVAL.  The backward forms take every gradient-source kind (the trunk's first layer of NewFluidNet sums
+ * a conv's and a pooling level's gradients). */
+int mc_gn_act_fwd_drop(const void* y, int32_t n, int32_t c, int32_t h, int32_t w, int32_t groups,
+                       const float* stats_ng2, const float* gamma, const float* beta, int32_t post,
+                       int32_t act, int32_t pool, int32_t dtype, void* a, void* pooled, const mc_dropout* drop, void* stream);
+int mc_gn_act_fwd_small_drop(const void* y, const float* stat_partials, int32_t tiles, int32_t n, int32_t c, int32_t h, int32_t w,
+                             int32_t groups, float eps, const float* gamma, const float* beta, int32_t act, int32_t pool,
+                             int32_t dtype, float* stats_ng2, void* a, void* pooled, const mc_dropout* drop, void* stream);
+int mc_gn_act_bwd_reduce_drop(const void* y, int32_t n, int32_t c, int32_t h, int32_t w, int32_t groups,
+                              const float* stats_ng2, const float* gamma, const float* beta, int32_t post,
+                              int32_t act, int32_t dtype, const mc_grad_src* g0, const mc_grad_src* g1,
+                              float* partials, const mc_dropout* drop, void* stream);
+int mc_gn_act_bwd_apply_drop(const void* y, int32_t n, int32_t c, int32_t h, int32_t w, int32_t groups,
+                             const float* stats_ng2, const float* m12_ng2, const float* gamma,
+                             const float* beta, int32_t post, int32_t act, int32_t dtype,
+                             const mc_grad_src* g0, const mc_grad_src* g1, void* dy, const mc_dropout* drop, void* stream);
+int mc_gn_act_bwd_small_drop(const void* y, int32_t n, int32_t c, int32_t h, int32_t w, int32_t groups, const float* stats_ng2,
+                             const float* gamma, const float* beta, int32_t act, int32_t dtype, const mc_grad_src* g0,
+                             const mc_grad_src* g1, void* dy, float* chan_sums, const mc_dropout* drop, void* stream);
+/* Host twins of the generator the kernels inline (no device needed): Philox4x32-10 itself, and the keep flags (0 / 1) of the
+ * 8 channels of the vectors first_vec .. first_vec + n_vec - 1 into out[n_vec * 8]. */
+void mc_philox4x32(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
+int mc_dropout_mask_host(uint32_t seed_lo, uint32_t seed_hi, uint32_t step, uint32_t layer, uint64_t first_vec, uint64_t n_vec,
+                         uint32_t keep16, uint8_t* out);
 /* Phase 3 for a tensor whose dz = dA * act'(z) was already written by mc_conv2d_fused's epilogue (+ mc_fold_padded_dz):
  * dy = scale * dz - rstd (m1 + yhat m2)  (coef = the layer's table, m12 from mc_gn_act_bwd_finalize); with coef == NULL
  * (activation-only layer) dy = dz.  dz is read through a gradient source (MC_GSRC_PADFOLD or MC_GSRC_PLAIN). */

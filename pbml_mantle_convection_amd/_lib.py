@@ -51,6 +51,19 @@ class ConvEpilogue(C.Structure):
                 ("y_f16", C.c_int32)]
 
 
+class Dropout(C.Structure):
+    """mc_dropout: device state (seed_lo, seed_hi, step, 0), the layer's id and the keep threshold T (kept iff field < T)."""
+    _fields_ = [("state", C.c_void_p), ("layer", C.c_uint32), ("keep16", C.c_uint32)]
+
+
+def dropout_keep16(p: float) -> int:
+    """T = clamp(round((1 - p) * 65536), 1, 65535): an element is kept with probability T / 65536 and scaled by
+    f32(65536 / T); the effective rate is quantised to 2^-16."""
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"dropout rate must satisfy 0 <= p < 1, got {p}")
+    return min(max(int(round((1.0 - p) * 65536.0)), 1), 65535)
+
+
 class LossDesc(C.Structure):
     _fields_ = [("n", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("p_pred", C.c_int32),
                 ("loss_type", C.c_int32), ("loss_scale", C.c_int32), ("loss_derivative", C.c_int32),
@@ -62,6 +75,7 @@ _vp, _i32, _i64, _f32, _sz = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_si
 _CD, _GS, _LD = C.POINTER(ConvDesc), C.POINTER(GradSrc), C.POINTER(LossDesc)
 _CP, _CE = C.POINTER(ConvPrologue), C.POINTER(ConvEpilogue)
 _LN = C.POINTER(LearnedDesc)
+_DR, _u32, _u64 = C.POINTER(Dropout), C.c_uint32, C.c_uint64
 
 # name -> (restype, argtypes); must list EVERY symbol include/mantle_hip.h declares
 SIGNATURES = {
@@ -106,6 +120,19 @@ SIGNATURES = {
     "mc_gn_act_fwd_small": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp,
                                       _vp]),
     "mc_gn_act_bwd_small": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _GS, _GS, _vp, _vp, _vp]),
+    "mc_dropout_advance": (C.c_int, [_vp, _vp]),
+    "mc_gn_act_fwd_drop": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp,
+                                     _vp, _DR, _vp]),
+    "mc_gn_act_fwd_small_drop": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _i32, _i32, _i32, _vp, _vp,
+                                           _vp, _DR, _vp]),
+    "mc_gn_act_bwd_reduce_drop": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _GS,
+                                            _GS, _vp, _DR, _vp]),
+    "mc_gn_act_bwd_apply_drop": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32,
+                                           _GS, _GS, _vp, _DR, _vp]),
+    "mc_gn_act_bwd_small_drop": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _GS, _GS, _vp, _vp,
+                                           _DR, _vp]),
+    "mc_philox4x32": (None, [C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32)]),
+    "mc_dropout_mask_host": (C.c_int, [_u32, _u32, _u32, _u32, _u64, _u64, _u32, _vp]),
     "mc_gn_param_grads_batched": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _vp]),
     "mc_avgpool_fwd": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "mc_rect_copy": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
@@ -163,7 +190,7 @@ SIGNATURES = {
 VALUE_RETURNING = {"mc_version", "mc_strerror", "mc_conv_kernel_name", "mc_packed_weight_bytes", "mc_conv_bank_read_extent", "mc_conv_tiles",
                    "mc_wgrad_partial_bytes", "mc_gn_bwd_blocks",
                    "mc_learned_validate", "mc_learned_bank_bytes", "mc_learned_wgrad_workspace_bytes", "mc_fold_blocks", "mc_loss_fused_blocks",
-                   "mc_spectral_slots"}
+                   "mc_spectral_slots", "mc_philox4x32"}
 
 _lib = None
 

@@ -2,6 +2,7 @@
 // curl head.  All HBM-bound streaming kernels over the CB8 layout: one thread moves one
 // 8-channel vector (32 B f32 / 16 B bf16), consecutive lanes take consecutive pixels.
 #include "common.h"
+#include "philox.h"
 
 namespace {
 
@@ -272,8 +273,25 @@ __device__ __forceinline__ void gn_coef(const GnArgs& a, int n, int cb, float (&
   }
 }
 
-template <typename T, int POOL>
-__global__ void k_gn_act_fwd(GnArgs a, const T* __restrict__ y, T* __restrict__ out, T* __restrict__ pooled) {
+// Dropout after the activation (nn.Dropout at the end of a FluidLayer): a compile-time variant (DROP) of the kernels below.
+// state = (seed_lo, seed_hi, step, 0) on the device; the mask of CB8 vector v is regenerated from it wherever it is needed
+// (forward, both backward passes), never stored (csrc/philox.h).  scale = f32(65536 / keep16).
+struct DropK { const uint32_t* state; uint32_t layer, keep16; float scale; };
+struct DropSeed { uint32_t lo, hi, step; };
+__device__ __forceinline__ DropSeed drop_seed(const DropK& d) { return DropSeed{d.state[0], d.state[1], d.state[2]}; }
+__device__ __forceinline__ uint64_t drop_base(int n, int cb, int C8, int H, int W) {
+  return ((uint64_t)n * C8 + cb) * (uint64_t)H * (uint64_t)W;
+}
+// ms[j] = kept ? scale : 0 for the 8 channels of vector v
+__device__ __forceinline__ void drop_factors(const DropK& d, const DropSeed& sd, uint64_t v, float (&ms)[8]) {
+  const uint32_t bits = mc_dropout_keep8(sd.lo, sd.hi, sd.step, d.layer, v, d.keep16);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) ms[j] = ((bits >> j) & 1u) ? d.scale : 0.f;
+}
+
+template <typename T, int POOL, bool DROP = false>
+__global__ void k_gn_act_fwd(GnArgs a, const T* __restrict__ y, T* __restrict__ out, T* __restrict__ pooled, DropK dk) {
+  static_assert(!DROP || POOL == 1, "dropout layers are not pooled in the same launch");
   // one thread per POOLxPOOL pixel block of one channel block
   const int Hb = (a.H + POOL - 1) / POOL, Wb = (a.W + POOL - 1) / POOL;
   const int Hp = a.H / POOL, Wp = a.W / POOL;
@@ -281,6 +299,9 @@ __global__ void k_gn_act_fwd(GnArgs a, const T* __restrict__ y, T* __restrict__ 
   float sc[8], sh[8];
   gn_coef(a, n, cb, sc, sh);
   const int act = a.post == MC_POST_NONE ? MC_ACT_NONE : a.act;
+  DropSeed sd = {0, 0, 0};
+  uint64_t vbase = 0;
+  if constexpr (DROP) { sd = drop_seed(dk); vbase = drop_base(n, cb, a.C8, a.H, a.W); }
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < Hb * Wb; i += gridDim.x * blockDim.x) {
     int by = i / Wb, bx = i % Wb;
     float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -294,6 +315,12 @@ __global__ void k_gn_act_fwd(GnArgs a, const T* __restrict__ y, T* __restrict__ 
           size_t idx = cb8_index(n, cb, yy, xx, a.C8, a.H, a.W);
           V8<T>::ld(y + idx, v);
           act_fwd8<FastMath<T>::value>(v, sc, sh, act, v);
+          if constexpr (DROP) {
+            float ms[8];
+            drop_factors(dk, sd, vbase + (uint32_t)(yy * a.W + xx), ms);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[j] *= ms[j];
+          }
 #pragma unroll
           for (int j = 0; j < 8; ++j) acc[j] += v[j];
           if (out) V8<T>::st(out + idx, v);
@@ -348,10 +375,11 @@ __global__ void k_gn_act_fwd_pool2_rows(GnArgs a, const T* __restrict__ y, T* __
 // Small layers: GroupNorm statistics from the conv's partial sums AND a = act(GN(y)) [+ AvgPool] in one launch, one block per
 // (sample, channel block); needs every group inside one channel block (channels per group 1, 2, 4 or 8).  The (mean, rstd)
 // pairs are also written out for the backward pass.  Same f64 sums and f32 expressions as k_gn_finalize / gn_coef.
-template <typename T, int POOL>
+template <typename T, int POOL, bool DROP = false>
 __global__ __launch_bounds__(1024) void k_gn_act_small(GnArgs a, const T* __restrict__ y, const float* __restrict__ part, int tiles,
                                                        float eps, float* __restrict__ stats_out, T* __restrict__ out,
-                                                       T* __restrict__ pooled) {
+                                                       T* __restrict__ pooled, DropK dk) {
+  static_assert(!DROP || POOL == 1, "dropout layers are not pooled in the same launch");
   const int n = (int)blockIdx.y, cb = blockIdx.x, CP = a.C8 * 8;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   __shared__ float s_mean[8], s_rstd[8];
@@ -389,6 +417,9 @@ __global__ __launch_bounds__(1024) void k_gn_act_small(GnArgs a, const T* __rest
   }
   const int Hb = (a.H + POOL - 1) / POOL, Wb = (a.W + POOL - 1) / POOL;
   const int Hp = a.H / POOL, Wp = a.W / POOL;
+  DropSeed sd = {0, 0, 0};
+  uint64_t vbase = 0;
+  if constexpr (DROP) { sd = drop_seed(dk); vbase = drop_base(n, cb, a.C8, a.H, a.W); }
   for (int i = threadIdx.x; i < Hb * Wb; i += blockDim.x) {
     const int by = i / Wb, bx = i - by * Wb;
     float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -402,6 +433,12 @@ __global__ __launch_bounds__(1024) void k_gn_act_small(GnArgs a, const T* __rest
           const size_t idx = cb8_index(n, cb, yy, xx, a.C8, a.H, a.W);
           V8<T>::ld(y + idx, v);
           act_fwd8<FastMath<T>::value>(v, sc, sh, a.act, v);
+          if constexpr (DROP) {
+            float ms[8];
+            drop_factors(dk, sd, vbase + (uint32_t)(yy * a.W + xx), ms);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[j] *= ms[j];
+          }
 #pragma unroll
           for (int j = 0; j < 8; ++j) acc[j] += v[j];
           V8<T>::st(out + idx, v);
@@ -454,9 +491,9 @@ static int gkind_of(const mc_grad_src& g0, const mc_grad_src& g1) {
 }
 
 // TY: storage type of y (MC_MIX16: y is f16 while the gradient tensors T are bf16)
-template <typename T, int GK, typename TY = T>
-__global__ __launch_bounds__(256, 6) void k_gn_bwd_reduce(GnArgs a, const TY* __restrict__ y, mc_grad_src g0,
-                                                       mc_grad_src g1, float* __restrict__ part, int CP) {
+template <typename T, int GK, typename TY = T, bool DROP = false>
+__global__ __launch_bounds__(256, DROP ? 5 : 6) void k_gn_bwd_reduce(GnArgs a, const TY* __restrict__ y, mc_grad_src g0,
+                                                       mc_grad_src g1, float* __restrict__ part, int CP, DropK dk) {
   const int n = (int)blockIdx.z, cb = blockIdx.y, blk = blockIdx.x, nblk = gridDim.x;
   float sc[8], sh[8], mean[8], rstd[8];
   gn_coef(a, n, cb, sc, sh);
@@ -479,6 +516,9 @@ __global__ __launch_bounds__(256, 6) void k_gn_bwd_reduce(GnArgs a, const TY* __
   // MC_GN_RED_UNROLL positions per iteration, every load issued before the first use: the loop is bound by the bytes it
   // keeps in flight (two 16-byte loads per position), not by arithmetic
   const int total = nrows * a.W;
+  DropSeed sd = {0, 0, 0};
+  uint64_t vbase = 0;
+  if constexpr (DROP) { sd = drop_seed(dk); vbase = drop_base(n, cb, a.C8, a.H, a.W); }
   for (int i0 = threadIdx.x; i0 < total; i0 += blockDim.x * MC_GN_RED_UNROLL) {
     float v[MC_GN_RED_UNROLL][8], da[MC_GN_RED_UNROLL][8];
 #pragma unroll
@@ -490,6 +530,12 @@ __global__ __launch_bounds__(256, 6) void k_gn_bwd_reduce(GnArgs a, const TY* __
       V8<TY>::ld(y + cb8_index(n, cb, yy, xx, a.C8, a.H, a.W), v[u]);
       grad_fetch_add<T, GKinds<GK>::k0>(g0, n, cb, yy, xx, a.C8, da[u]);
       grad_fetch_add<T, GKinds<GK>::k1>(g1, n, cb, yy, xx, a.C8, da[u]);
+      if constexpr (DROP) {
+        float ms[8];
+        drop_factors(dk, sd, vbase + (uint32_t)(yy * a.W + xx), ms);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) da[u][j] *= ms[j];
+      }
     }
 #pragma unroll
     for (int u = 0; u < MC_GN_RED_UNROLL; ++u) {
@@ -639,9 +685,9 @@ __global__ __launch_bounds__(256) void k_gn_bwd_finalize_n(const float* __restri
 }
 
 // phase 3: dy = rstd (dz gamma - m1 - yhat m2)   (GN)   |   dy = da act'(y)   (act only)
-template <typename T, int GK = 0, typename TY = T>
+template <typename T, int GK = 0, typename TY = T, bool DROP = false>
 __global__ __launch_bounds__(256) void k_gn_bwd_apply(GnArgs a, const TY* __restrict__ y, const float* __restrict__ m12,
-                                                      mc_grad_src g0, mc_grad_src g1, T* __restrict__ dy, int rows_pb) {
+                                                      mc_grad_src g0, mc_grad_src g1, T* __restrict__ dy, int rows_pb, DropK dk) {
   const int n = (int)blockIdx.z, cb = blockIdx.y;
   float sc[8], sh[8], mean[8], rstd[8], ga[8], m1[8], m2[8];
   gn_coef(a, n, cb, sc, sh);
@@ -671,6 +717,9 @@ __global__ __launch_bounds__(256) void k_gn_bwd_apply(GnArgs a, const TY* __rest
   // vectors per thread (one vector per thread left these kernels latency-bound at ~1.3 TB/s).  (A 4-way manual batching
   // of the loads was tried and was SLOWER: 131 VGPRs cut the occupancy of this streaming kernel.)
   const int y0 = blockIdx.x * rows_pb, nrows = min(rows_pb, a.H - y0);
+  DropSeed sd = {0, 0, 0};
+  uint64_t vbase = 0;
+  if constexpr (DROP) { sd = drop_seed(dk); vbase = drop_base(n, cb, a.C8, a.H, a.W); }
   for (int i = threadIdx.x; i < nrows * a.W; i += blockDim.x) {      // rows x columns flattened (narrow images)
     const int ry = i / a.W, xx = i - ry * a.W, yy = y0 + ry;
     float v[8], da[8] = {0, 0, 0, 0, 0, 0, 0, 0}, o[8];
@@ -678,6 +727,12 @@ __global__ __launch_bounds__(256) void k_gn_bwd_apply(GnArgs a, const TY* __rest
     V8<TY>::ld(y + idx, v);
     grad_fetch_add<T, GKinds<GK>::k0>(g0, n, cb, yy, xx, a.C8, da);
     grad_fetch_add<T, GKinds<GK>::k1>(g1, n, cb, yy, xx, a.C8, da);
+    if constexpr (DROP) {
+      float ms[8];
+      drop_factors(dk, sd, vbase + (uint32_t)(yy * a.W + xx), ms);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) da[j] *= ms[j];
+    }
     float gz[8];
     act_bwd8<FastMath<T>::value>(v, sc, sh, a.act, gz);
     // dy = rstd (gamma dz - m1 - yhat m2) = cA dz + cB (y - mean) + cC  (three packed FMAs per channel pair)
@@ -698,9 +753,9 @@ __global__ __launch_bounds__(256) void k_gn_bwd_apply(GnArgs a, const TY* __rest
 // data: they are bound by launch latency, not by bytes.  Needs every group inside one channel block (channels per group
 // 1, 2, 4 or 8).  The per-(sample, channel) sums go to `pc` [N][CP][2]; k_gn_param_grads adds them to dgamma / dbeta in sample
 // order for all such layers at the end of the backward pass.
-template <typename T, int GK, typename TY = T>
+template <typename T, int GK, typename TY = T, bool DROP = false>
 __global__ __launch_bounds__(1024) void k_gn_bwd_small(GnArgs a, const TY* __restrict__ y, mc_grad_src g0, mc_grad_src g1,
-                                                       T* __restrict__ dy, float* __restrict__ pc, int CP) {
+                                                       T* __restrict__ dy, float* __restrict__ pc, int CP, DropK dk) {
   const int n = (int)blockIdx.y, cb = blockIdx.x;
   float sc[8], sh[8], mean[8], rstd[8], ga[8];
   gn_coef(a, n, cb, sc, sh);
@@ -716,6 +771,9 @@ __global__ __launch_bounds__(1024) void k_gn_bwd_small(GnArgs a, const TY* __res
     }
   }
   const int total = a.H * a.W;
+  DropSeed sd = {0, 0, 0};
+  uint64_t vbase = 0;
+  if constexpr (DROP) { sd = drop_seed(dk); vbase = drop_base(n, cb, a.C8, a.H, a.W); }
   float s[16];
 #pragma unroll
   for (int j = 0; j < 16; ++j) s[j] = 0.f;
@@ -725,6 +783,12 @@ __global__ __launch_bounds__(1024) void k_gn_bwd_small(GnArgs a, const TY* __res
     V8<TY>::ld(y + cb8_index(n, cb, yy, xx, a.C8, a.H, a.W), v);
     grad_fetch_add<T, GKinds<GK>::k0>(g0, n, cb, yy, xx, a.C8, da);
     grad_fetch_add<T, GKinds<GK>::k1>(g1, n, cb, yy, xx, a.C8, da);
+    if constexpr (DROP) {                                   // (the same Philox call in both walks: the mask is not kept in registers)
+      float ms[8];
+      drop_factors(dk, sd, vbase + (uint32_t)i, ms);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) da[j] *= ms[j];
+    }
     act_bwd8<FastMath<T>::value>(v, sc, sh, a.act, gz);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
@@ -777,6 +841,12 @@ __global__ __launch_bounds__(1024) void k_gn_bwd_small(GnArgs a, const TY* __res
     V8<TY>::ld(y + idx, v);
     grad_fetch_add<T, GKinds<GK>::k0>(g0, n, cb, yy, xx, a.C8, da);
     grad_fetch_add<T, GKinds<GK>::k1>(g1, n, cb, yy, xx, a.C8, da);
+    if constexpr (DROP) {                                   // (the same Philox call in both walks: the mask is not kept in registers)
+      float ms[8];
+      drop_factors(dk, sd, vbase + (uint32_t)i, ms);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) da[j] *= ms[j];
+    }
     act_bwd8<FastMath<T>::value>(v, sc, sh, a.act, gz);
 #pragma unroll
     for (int j = 0; j < 8; j += 2) {
@@ -1931,12 +2001,27 @@ static int fill_gn_args(GnArgs& a, int n, int c, int h, int w, int groups, const
   return MC_OK;
 }
 
-int mc_gn_act_fwd(const void* y, int32_t n, int32_t c, int32_t h, int32_t w, int32_t groups, const float* stats,
-                  const float* gamma, const float* beta, int32_t post, int32_t act, int32_t pool, int32_t dtype,
-                  void* a_out, void* pooled, void* stream) {
+// dropout descriptor of the C ABI -> kernel argument (drop == NULL: the plain kernels; *ok = 0 on a malformed descriptor)
+static DropK drop_args(const mc_dropout* d, int* ok) {
+  DropK k = {nullptr, 0u, 0u, 0.f};
+  *ok = 1;
+  if (!d) return k;
+  if (!d->state || d->keep16 < 1u || d->keep16 > 65535u) { *ok = 0; return k; }
+  k.state = d->state; k.layer = d->layer; k.keep16 = d->keep16;
+  k.scale = (float)(65536.0 / (double)d->keep16);
+  return k;
+}
+
+static int gn_act_fwd(const void* y, int32_t n, int32_t c, int32_t h, int32_t w, int32_t groups, const float* stats,
+                      const float* gamma, const float* beta, int32_t post, int32_t act, int32_t pool, int32_t dtype,
+                      void* a_out, void* pooled, const mc_dropout* drop, void* stream) {
   GnArgs a;
   int rc = fill_gn_args(a, n, c, h, w, groups, stats, gamma, beta, post, act);
   if (rc) return rc;
+  int dok;
+  const DropK dk = drop_args(drop, &dok);
+  if (!dok) return MC_EINVAL;
+  if (drop && pool != 1) return MC_EUNSUPPORTED;
   if (!y || (!a_out && pool == 1) || (pool > 1 && !pooled)) return MC_EINVAL;
   if (pool != 1 && pool != 2 && pool != 4) return MC_EUNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;
@@ -1950,14 +2035,31 @@ int mc_gn_act_fwd(const void* y, int32_t n, int32_t c, int32_t h, int32_t w, int
     MC_CHECK_LAUNCH();
     return MC_OK;
   }
-#define GN_LAUNCH(T, P) hipLaunchKernelGGL((k_gn_act_fwd<T, P>), g, dim3(256), 0, s, a, (const T*)y, (T*)a_out, (T*)pooled)
+#define GN_LAUNCH(T, P) hipLaunchKernelGGL((k_gn_act_fwd<T, P>), g, dim3(256), 0, s, a, (const T*)y, (T*)a_out, (T*)pooled, dk)
+#define GN_DROP(T) hipLaunchKernelGGL((k_gn_act_fwd<T, 1, true>), g, dim3(256), 0, s, a, (const T*)y, (T*)a_out, (T*)pooled, dk)
+  if (drop) {
+    if (dtype == MC_F32) GN_DROP(float); else if (dtype == MC_BF16) GN_DROP(bf16_t); else if (dtype == MC_MIX16) GN_DROP(f16_t);
+    else return MC_EUNSUPPORTED;
+  } else
   if (dtype == MC_F32) { if (pool == 1) GN_LAUNCH(float, 1); else if (pool == 2) GN_LAUNCH(float, 2); else GN_LAUNCH(float, 4); }
   else if (dtype == MC_BF16) { if (pool == 1) GN_LAUNCH(bf16_t, 1); else if (pool == 2) GN_LAUNCH(bf16_t, 2); else GN_LAUNCH(bf16_t, 4); }
   else if (dtype == MC_MIX16) { if (pool == 1) GN_LAUNCH(f16_t, 1); else if (pool == 2) GN_LAUNCH(f16_t, 2); else GN_LAUNCH(f16_t, 4); }
   else return MC_EUNSUPPORTED;
+#undef GN_DROP
 #undef GN_LAUNCH
   MC_CHECK_LAUNCH();
   return MC_OK;
+}
+int mc_gn_act_fwd(const void* y, int32_t n, int32_t c, int32_t h, int32_t w, int32_t groups, const float* stats,
+                  const float* gamma, const float* beta, int32_t post, int32_t act, int32_t pool, int32_t dtype,
+                  void* a_out, void* pooled, void* stream) {
+  return gn_act_fwd(y, n, c, h, w, groups, stats, gamma, beta, post, act, pool, dtype, a_out, pooled, nullptr, stream);
+}
+int mc_gn_act_fwd_drop(const void* y, int32_t n, int32_t c, int32_t h, int32_t w, int32_t groups, const float* stats,
+                       const float* gamma, const float* beta, int32_t post, int32_t act, int32_t pool, int32_t dtype,
+                       void* a_out, void* pooled, const mc_dropout* drop, void* stream) {
+  if (!drop) return MC_EINVAL;
+  return gn_act_fwd(y, n, c, h, w, groups, stats, gamma, beta, post, act, pool, dtype, a_out, pooled, drop, stream);
 }
 
 int mc_avgpool_fwd(const void* x, int32_t n, int32_t c, int32_t h, int32_t w, int32_t f, int32_t dtype, void* out,
@@ -2002,29 +2104,50 @@ static mc_grad_src gsrc_or_none(const mc_grad_src* g) {
   return g ? *g : z;
 }
 
-int mc_gn_act_bwd_reduce(const void* y, int32_t n, int32_t c, int32_t h, int32_t w, int32_t groups, const float* stats,
-                         const float* gamma, const float* beta, int32_t post, int32_t act, int32_t dtype,
-                         const mc_grad_src* g0, const mc_grad_src* g1, float* partials, void* stream) {
+static int gn_act_bwd_reduce(const void* y, int32_t n, int32_t c, int32_t h, int32_t w, int32_t groups, const float* stats,
+                             const float* gamma, const float* beta, int32_t post, int32_t act, int32_t dtype,
+                             const mc_grad_src* g0, const mc_grad_src* g1, float* partials, const mc_dropout* drop, void* stream) {
   GnArgs a;
   int rc = fill_gn_args(a, n, c, h, w, groups, stats, gamma, beta, post, act);
   if (rc) return rc;
+  int dok;
+  const DropK dk = drop_args(drop, &dok);
+  if (!dok) return MC_EINVAL;
   if (post != MC_POST_GN_ACT || !y || !partials || !g0) return MC_EINVAL;
   if ((rc = check_gsrc(g0)) || (rc = check_gsrc(g1))) return rc;
   dim3 g(mc_gn_bwd_blocks(h, w), a.C8, n);
   hipStream_t s = (hipStream_t)stream;
   const mc_grad_src s0 = gsrc_or_none(g0), s1 = gsrc_or_none(g1);
-#define RED(T, GK) hipLaunchKernelGGL((k_gn_bwd_reduce<T, GK>), g, dim3(256), 0, s, a, (const T*)y, s0, s1, partials, a.C8 * 8)
-#define REDH(GK) hipLaunchKernelGGL((k_gn_bwd_reduce<bf16_t, GK, f16_t>), g, dim3(256), 0, s, a, (const f16_t*)y, s0, s1, partials, a.C8 * 8)
+#define RED(T, GK) hipLaunchKernelGGL((k_gn_bwd_reduce<T, GK>), g, dim3(256), 0, s, a, (const T*)y, s0, s1, partials, a.C8 * 8, dk)
+#define REDH(GK) hipLaunchKernelGGL((k_gn_bwd_reduce<bf16_t, GK, f16_t>), g, dim3(256), 0, s, a, (const f16_t*)y, s0, s1, partials, a.C8 * 8, dk)
+#define RED_DROP(T, TY) hipLaunchKernelGGL((k_gn_bwd_reduce<T, 0, TY, true>), g, dim3(256), 0, s, a, (const TY*)y, s0, s1, partials, a.C8 * 8, dk)
+  if (drop) {             // (source kinds decided at run time: the Philox rounds, not the fetch, bound these variants)
+    if (dtype == MC_F32) RED_DROP(float, float); else if (dtype == MC_BF16) RED_DROP(bf16_t, bf16_t);
+    else if (dtype == MC_MIX16) RED_DROP(bf16_t, f16_t); else return MC_EUNSUPPORTED;
+  } else
   if (dtype == MC_F32) RED(float, 0);
   else if (dtype == MC_BF16) {
     switch (gkind_of(s0, s1)) { case 1: RED(bf16_t, 1); break; case 2: RED(bf16_t, 2); break; case 3: RED(bf16_t, 3); break; default: RED(bf16_t, 0); }
   } else if (dtype == MC_MIX16) {
     switch (gkind_of(s0, s1)) { case 1: REDH(1); break; case 2: REDH(2); break; case 3: REDH(3); break; default: REDH(0); }
   } else return MC_EUNSUPPORTED;
+#undef RED_DROP
 #undef REDH
 #undef RED
   MC_CHECK_LAUNCH();
   return MC_OK;
+}
+int mc_gn_act_bwd_reduce(const void* y, int32_t n, int32_t c, int32_t h, int32_t w, int32_t groups, const float* stats,
+                         const float* gamma, const float* beta, int32_t post, int32_t act, int32_t dtype,
+                         const mc_grad_src* g0, const mc_grad_src* g1, float* partials, void* stream) {
+  return gn_act_bwd_reduce(y, n, c, h, w, groups, stats, gamma, beta, post, act, dtype, g0, g1, partials, nullptr, stream);
+}
+int mc_gn_act_bwd_reduce_drop(const void* y, int32_t n, int32_t c, int32_t h, int32_t w, int32_t groups, const float* stats,
+                              const float* gamma, const float* beta, int32_t post, int32_t act, int32_t dtype,
+                              const mc_grad_src* g0, const mc_grad_src* g1, float* partials, const mc_dropout* drop,
+                              void* stream) {
+  if (!drop) return MC_EINVAL;
+  return gn_act_bwd_reduce(y, n, c, h, w, groups, stats, gamma, beta, post, act, dtype, g0, g1, partials, drop, stream);
 }
 
 int mc_gn_act_bwd_finalize(const float* partials, int32_t n, int32_t blocks, int32_t c, int32_t groups, int32_t hw,
@@ -2047,12 +2170,16 @@ int mc_gn_act_bwd_finalize_n(const float* partials, int32_t n, int32_t blocks, i
   return MC_OK;
 }
 
-int mc_gn_act_bwd_apply(const void* y, int32_t n, int32_t c, int32_t h, int32_t w, int32_t groups, const float* stats,
-                        const float* m12, const float* gamma, const float* beta, int32_t post, int32_t act,
-                        int32_t dtype, const mc_grad_src* g0, const mc_grad_src* g1, void* dy, void* stream) {
+static int gn_act_bwd_apply(const void* y, int32_t n, int32_t c, int32_t h, int32_t w, int32_t groups, const float* stats,
+                            const float* m12, const float* gamma, const float* beta, int32_t post, int32_t act,
+                            int32_t dtype, const mc_grad_src* g0, const mc_grad_src* g1, void* dy, const mc_dropout* drop,
+                            void* stream) {
   GnArgs a;
   int rc = fill_gn_args(a, n, c, h, w, groups, stats, gamma, beta, post, act);
   if (rc) return rc;
+  int dok;
+  const DropK dk = drop_args(drop, &dok);
+  if (!dok) return MC_EINVAL;
   if (!y || !dy || !g0 || (post == MC_POST_GN_ACT && !m12)) return MC_EINVAL;
   if ((rc = check_gsrc(g0)) || (rc = check_gsrc(g1))) return rc;
   if (post == MC_POST_NONE) a.act = MC_ACT_NONE;
@@ -2060,47 +2187,91 @@ int mc_gn_act_bwd_apply(const void* y, int32_t n, int32_t c, int32_t h, int32_t 
   dim3 g(cdiv(h, rows), a.C8, n);
   hipStream_t s = (hipStream_t)stream;
   const mc_grad_src s0 = gsrc_or_none(g0), s1 = gsrc_or_none(g1);
-#define APP(T, GK) hipLaunchKernelGGL((k_gn_bwd_apply<T, GK>), g, dim3(256), 0, s, a, (const T*)y, m12, s0, s1, (T*)dy, rows)
-#define APPH(GK) hipLaunchKernelGGL((k_gn_bwd_apply<bf16_t, GK, f16_t>), g, dim3(256), 0, s, a, (const f16_t*)y, m12, s0, s1, (bf16_t*)dy, rows)
+#define APP(T, GK) hipLaunchKernelGGL((k_gn_bwd_apply<T, GK>), g, dim3(256), 0, s, a, (const T*)y, m12, s0, s1, (T*)dy, rows, dk)
+#define APPH(GK) hipLaunchKernelGGL((k_gn_bwd_apply<bf16_t, GK, f16_t>), g, dim3(256), 0, s, a, (const f16_t*)y, m12, s0, s1, (bf16_t*)dy, rows, dk)
+#define APP_DROP(T, TY) hipLaunchKernelGGL((k_gn_bwd_apply<T, 0, TY, true>), g, dim3(256), 0, s, a, (const TY*)y, m12, s0, s1, (T*)dy, rows, dk)
+  if (drop) {
+    if (dtype == MC_F32) APP_DROP(float, float); else if (dtype == MC_BF16) APP_DROP(bf16_t, bf16_t);
+    else if (dtype == MC_MIX16) APP_DROP(bf16_t, f16_t); else return MC_EUNSUPPORTED;
+  } else
   if (dtype == MC_F32) APP(float, 0);
   else if (dtype == MC_BF16) {
     switch (gkind_of(s0, s1)) { case 1: APP(bf16_t, 1); break; case 2: APP(bf16_t, 2); break; case 3: APP(bf16_t, 3); break; default: APP(bf16_t, 0); }
   } else if (dtype == MC_MIX16) {
     switch (gkind_of(s0, s1)) { case 1: APPH(1); break; case 2: APPH(2); break; case 3: APPH(3); break; default: APPH(0); }
   } else return MC_EUNSUPPORTED;
+#undef APP_DROP
 #undef APPH
 #undef APP
   MC_CHECK_LAUNCH();
   return MC_OK;
 }
+int mc_gn_act_bwd_apply(const void* y, int32_t n, int32_t c, int32_t h, int32_t w, int32_t groups, const float* stats,
+                        const float* m12, const float* gamma, const float* beta, int32_t post, int32_t act,
+                        int32_t dtype, const mc_grad_src* g0, const mc_grad_src* g1, void* dy, void* stream) {
+  return gn_act_bwd_apply(y, n, c, h, w, groups, stats, m12, gamma, beta, post, act, dtype, g0, g1, dy, nullptr, stream);
+}
+int mc_gn_act_bwd_apply_drop(const void* y, int32_t n, int32_t c, int32_t h, int32_t w, int32_t groups, const float* stats,
+                             const float* m12, const float* gamma, const float* beta, int32_t post, int32_t act,
+                             int32_t dtype, const mc_grad_src* g0, const mc_grad_src* g1, void* dy, const mc_dropout* drop,
+                             void* stream) {
+  if (!drop) return MC_EINVAL;
+  return gn_act_bwd_apply(y, n, c, h, w, groups, stats, m12, gamma, beta, post, act, dtype, g0, g1, dy, drop, stream);
+}
 
-int mc_gn_act_fwd_small(const void* y, const float* stat_partials, int32_t tiles, int32_t n, int32_t c, int32_t h, int32_t w,
-                        int32_t groups, float eps, const float* gamma, const float* beta, int32_t act, int32_t pool,
-                        int32_t dtype, float* stats_out, void* a_out, void* pooled, void* stream) {
+static int gn_act_fwd_small(const void* y, const float* stat_partials, int32_t tiles, int32_t n, int32_t c, int32_t h, int32_t w,
+                            int32_t groups, float eps, const float* gamma, const float* beta, int32_t act, int32_t pool,
+                            int32_t dtype, float* stats_out, void* a_out, void* pooled, const mc_dropout* drop, void* stream) {
   GnArgs a;
   int rc = fill_gn_args(a, n, c, h, w, groups, stats_out, gamma, beta, MC_POST_GN_ACT, act);
   if (rc) return rc;
+  int dok;
+  const DropK dk = drop_args(drop, &dok);
+  if (!dok) return MC_EINVAL;
+  if (drop && pool != 1) return MC_EUNSUPPORTED;
   if (!y || !stat_partials || tiles <= 0 || !gamma || !beta || !stats_out || !a_out || (pool > 1 && !pooled)) return MC_EINVAL;
   if (pool != 1 && pool != 2) return MC_EUNSUPPORTED;
   if (a.cpg != 1 && a.cpg != 2 && a.cpg != 4 && a.cpg != 8) return MC_EUNSUPPORTED;
   dim3 g(a.C8, n);
   hipStream_t s = (hipStream_t)stream;
-#define FS(T, P) hipLaunchKernelGGL((k_gn_act_small<T, P>), g, dim3(gn_small_threads(a.C8 * n)), 0, s, a, (const T*)y, stat_partials, tiles, eps, stats_out, (T*)a_out, (T*)pooled)
+#define FS(T, P) hipLaunchKernelGGL((k_gn_act_small<T, P>), g, dim3(gn_small_threads(a.C8 * n)), 0, s, a, (const T*)y, stat_partials, tiles, eps, stats_out, (T*)a_out, (T*)pooled, dk)
+#define FS_DROP(T) hipLaunchKernelGGL((k_gn_act_small<T, 1, true>), g, dim3(gn_small_threads(a.C8 * n)), 0, s, a, (const T*)y, stat_partials, tiles, eps, stats_out, (T*)a_out, (T*)pooled, dk)
+  if (drop) {
+    if (dtype == MC_F32) FS_DROP(float); else if (dtype == MC_BF16) FS_DROP(bf16_t); else if (dtype == MC_MIX16) FS_DROP(f16_t);
+    else return MC_EUNSUPPORTED;
+  } else
   if (dtype == MC_F32) { if (pool == 1) FS(float, 1); else FS(float, 2); }
   else if (dtype == MC_BF16) { if (pool == 1) FS(bf16_t, 1); else FS(bf16_t, 2); }
   else if (dtype == MC_MIX16) { if (pool == 1) FS(f16_t, 1); else FS(f16_t, 2); }
   else return MC_EUNSUPPORTED;
+#undef FS_DROP
 #undef FS
   MC_CHECK_LAUNCH();
   return MC_OK;
 }
+int mc_gn_act_fwd_small(const void* y, const float* stat_partials, int32_t tiles, int32_t n, int32_t c, int32_t h, int32_t w,
+                        int32_t groups, float eps, const float* gamma, const float* beta, int32_t act, int32_t pool,
+                        int32_t dtype, float* stats_out, void* a_out, void* pooled, void* stream) {
+  return gn_act_fwd_small(y, stat_partials, tiles, n, c, h, w, groups, eps, gamma, beta, act, pool, dtype, stats_out, a_out, pooled,
+                          nullptr, stream);
+}
+int mc_gn_act_fwd_small_drop(const void* y, const float* stat_partials, int32_t tiles, int32_t n, int32_t c, int32_t h, int32_t w,
+                             int32_t groups, float eps, const float* gamma, const float* beta, int32_t act, int32_t pool,
+                             int32_t dtype, float* stats_out, void* a_out, void* pooled, const mc_dropout* drop, void* stream) {
+  if (!drop) return MC_EINVAL;
+  return gn_act_fwd_small(y, stat_partials, tiles, n, c, h, w, groups, eps, gamma, beta, act, pool, dtype, stats_out, a_out, pooled,
+                          drop, stream);
+}
 
-int mc_gn_act_bwd_small(const void* y, int32_t n, int32_t c, int32_t h, int32_t w, int32_t groups, const float* stats,
-                        const float* gamma, const float* beta, int32_t act, int32_t dtype, const mc_grad_src* g0,
-                        const mc_grad_src* g1, void* dy, float* chan_sums, void* stream) {
+static int gn_act_bwd_small(const void* y, int32_t n, int32_t c, int32_t h, int32_t w, int32_t groups, const float* stats,
+                            const float* gamma, const float* beta, int32_t act, int32_t dtype, const mc_grad_src* g0,
+                            const mc_grad_src* g1, void* dy, float* chan_sums, const mc_dropout* drop, void* stream) {
   GnArgs a;
   int rc = fill_gn_args(a, n, c, h, w, groups, stats, gamma, beta, MC_POST_GN_ACT, act);
   if (rc) return rc;
+  int dok;
+  const DropK dk = drop_args(drop, &dok);
+  if (!dok) return MC_EINVAL;
   if (!y || !dy || !g0 || !stats || !gamma || !beta || !chan_sums) return MC_EINVAL;
   if (a.cpg != 1 && a.cpg != 2 && a.cpg != 4 && a.cpg != 8) return MC_EUNSUPPORTED;     // a group must lie inside one channel block
   if ((rc = check_gsrc(g0)) || (rc = check_gsrc(g1))) return rc;
@@ -2108,17 +2279,60 @@ int mc_gn_act_bwd_small(const void* y, int32_t n, int32_t c, int32_t h, int32_t 
   hipStream_t s = (hipStream_t)stream;
   const mc_grad_src s0 = gsrc_or_none(g0), s1 = gsrc_or_none(g1);
   const int CP = a.C8 * 8;
-#define SM(T, GK) hipLaunchKernelGGL((k_gn_bwd_small<T, GK>), g, dim3(gn_small_threads(a.C8 * n)), 0, s, a, (const T*)y, s0, s1, (T*)dy, chan_sums, CP)
-#define SMH(GK) hipLaunchKernelGGL((k_gn_bwd_small<bf16_t, GK, f16_t>), g, dim3(gn_small_threads(a.C8 * n)), 0, s, a, (const f16_t*)y, s0, s1, (bf16_t*)dy, chan_sums, CP)
+#define SM(T, GK) hipLaunchKernelGGL((k_gn_bwd_small<T, GK>), g, dim3(gn_small_threads(a.C8 * n)), 0, s, a, (const T*)y, s0, s1, (T*)dy, chan_sums, CP, dk)
+#define SMH(GK) hipLaunchKernelGGL((k_gn_bwd_small<bf16_t, GK, f16_t>), g, dim3(gn_small_threads(a.C8 * n)), 0, s, a, (const f16_t*)y, s0, s1, (bf16_t*)dy, chan_sums, CP, dk)
+#define SM_DROP(T, TY) hipLaunchKernelGGL((k_gn_bwd_small<T, 0, TY, true>), g, dim3(gn_small_threads(a.C8 * n)), 0, s, a, (const TY*)y, s0, s1, (T*)dy, chan_sums, CP, dk)
+  if (drop) {
+    if (dtype == MC_F32) SM_DROP(float, float); else if (dtype == MC_BF16) SM_DROP(bf16_t, bf16_t);
+    else if (dtype == MC_MIX16) SM_DROP(bf16_t, f16_t); else return MC_EUNSUPPORTED;
+  } else
   if (dtype == MC_F32) SM(float, 0);
   else if (dtype == MC_BF16) {
     switch (gkind_of(s0, s1)) { case 1: SM(bf16_t, 1); break; case 2: SM(bf16_t, 2); break; case 3: SM(bf16_t, 3); break; default: SM(bf16_t, 0); }
   } else if (dtype == MC_MIX16) {
     switch (gkind_of(s0, s1)) { case 1: SMH(1); break; case 2: SMH(2); break; case 3: SMH(3); break; default: SMH(0); }
   } else return MC_EUNSUPPORTED;
+#undef SM_DROP
 #undef SMH
 #undef SM
   MC_CHECK_LAUNCH();
+  return MC_OK;
+}
+int mc_gn_act_bwd_small(const void* y, int32_t n, int32_t c, int32_t h, int32_t w, int32_t groups, const float* stats,
+                        const float* gamma, const float* beta, int32_t act, int32_t dtype, const mc_grad_src* g0,
+                        const mc_grad_src* g1, void* dy, float* chan_sums, void* stream) {
+  return gn_act_bwd_small(y, n, c, h, w, groups, stats, gamma, beta, act, dtype, g0, g1, dy, chan_sums, nullptr, stream);
+}
+int mc_gn_act_bwd_small_drop(const void* y, int32_t n, int32_t c, int32_t h, int32_t w, int32_t groups, const float* stats,
+                             const float* gamma, const float* beta, int32_t act, int32_t dtype, const mc_grad_src* g0,
+                             const mc_grad_src* g1, void* dy, float* chan_sums, const mc_dropout* drop, void* stream) {
+  if (!drop) return MC_EINVAL;
+  return gn_act_bwd_small(y, n, c, h, w, groups, stats, gamma, beta, act, dtype, g0, g1, dy, chan_sums, drop, stream);
+}
+
+// ---- dropout state and the host twins of the generator (csrc/philox.h) -------------------------
+__global__ void k_dropout_advance(uint32_t* __restrict__ state) { state[2] += 1u; }
+
+int mc_dropout_advance(uint32_t* state, void* stream) {
+  if (!state) return MC_EINVAL;
+  hipLaunchKernelGGL(k_dropout_advance, dim3(1), dim3(1), 0, (hipStream_t)stream, state);
+  MC_CHECK_LAUNCH();
+  return MC_OK;
+}
+
+void mc_philox4x32(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]) {
+  uint32_t o[4];
+  mc_philox4x32_10(ctr[0], ctr[1], ctr[2], ctr[3], key[0], key[1], o);
+  for (int i = 0; i < 4; ++i) out[i] = o[i];
+}
+
+int mc_dropout_mask_host(uint32_t seed_lo, uint32_t seed_hi, uint32_t step, uint32_t layer, uint64_t first_vec, uint64_t n_vec,
+                         uint32_t keep16, uint8_t* out) {
+  if (!out || keep16 < 1u || keep16 > 65535u) return MC_EINVAL;
+  for (uint64_t i = 0; i < n_vec; ++i) {
+    const uint32_t bits = mc_dropout_keep8(seed_lo, seed_hi, step, layer, first_vec + i, keep16);
+    for (int j = 0; j < 8; ++j) out[i * 8 + j] = (uint8_t)((bits >> j) & 1u);
+  }
   return MC_OK;
 }
 

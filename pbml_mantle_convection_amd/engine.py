@@ -54,6 +54,8 @@ class ConvNode:
     sym_v: int = 0             # y-mirrored filters / filters mirrored about both axes (SymmetricConv2d symmetry 'v' / 'hv';
     sym_hv: int = 0            # FluidLayer never sets them, reference :755-757)
     spectral: bool = False     # SpectralConv2d (reference :571-635): name + {weights1, weights2}, no bias; k = pad = sym = 0
+    drop: float = 0.0          # nn.Dropout(p) after the activation (FluidLayer, reference :753, :798); training mode only
+    layer: int = -1            # index among the graph's conv nodes in node order: the dropout mask's layer id
 
 
 @dataclass
@@ -129,20 +131,29 @@ class _Builder:
                         fluid_sym_h(c_out) if (symm and self.use_symm) else 0, post, gn_name, groups, pool, learned=self.learned, **bc)
         if pool > 1:
             node.pooled = self.new(c_out)
+        return self._append(node)
+
+    def _append(self, node):
+        node.layer = sum(1 for n in self.nodes if n.kind == "conv")
         self.nodes.append(node)
         return node
 
-    def fluid(self, prefix, srcs, c_out, spectral=False, **kw):
-        """A FluidLayer: conv + GroupNorm + activation; spectral: a SpectralFluidLayer (reference :638-699), whose GroupNorm
-        has int(c_o / 4) groups."""
+    def fluid(self, prefix, srcs, c_out, spectral=False, drop=0.0, **kw):
+        """A FluidLayer: conv + GroupNorm + activation (+ dropout with rate `drop` in training mode); spectral: a
+        SpectralFluidLayer (reference :638-699), whose GroupNorm has int(c_o / 4) groups and which has no dropout."""
         if spectral:
             if c_out < 4:
                 raise ValueError(f"{prefix}: a spectral layer needs c_o >= 4 (GroupNorm has int(c_o / 4) groups), got {c_out}")
             node = ConvNode(prefix + "layers.0.", list(srcs), self.new(c_out), c_out, 0, 0, 0, L.POST_GN_ACT, prefix + "layers.1.",
                             int(c_out / 4), spectral=True, **kw)
-            self.nodes.append(node)
-            return node
-        return self.conv(prefix + "layers.0.", srcs, c_out, L.POST_GN_ACT, prefix + "layers.1.", fluid_groups(c_out), symm=True, **kw)
+            return self._append(node)
+        node = self.conv(prefix + "layers.0.", srcs, c_out, L.POST_GN_ACT, prefix + "layers.1.", fluid_groups(c_out), symm=True, **kw)
+        if drop:
+            L.dropout_keep16(drop)                   # 0 <= p < 1, else ValueError
+            if node.pool > 1:
+                raise NotImplementedError(f"{prefix}: dropout on a layer that is pooled in its own launch is not built")
+            node.drop = float(drop)
+        return node
 
 
 def unet_graph(levels, c_i, c_h, c_o, *, act, r_p, use_symm, repeats, f) -> NetGraph:
@@ -250,20 +261,21 @@ def convae_graph(levels, c_i, c_h, c_o, *, act, r_p, use_symm, repeats, f, loss_
     return NetGraph(c_i, int(c_o), b.ch, b.nodes, pad_mode=r_p, act=act, divisor=4 ** levels)
 
 
-def _fluid_trunk(levels, c_i, c_h, *, r_p, use_symm, repeats, f, factor, spectral=False):
+def _fluid_trunk(levels, c_i, c_h, *, r_p, use_symm, repeats, f, factor, spectral=False, drop_rate=0.0):
     """The multi-resolution trunk NewFluidNet and FluidNet share (reference pytorch_networks_convae.py:1315-1337 and
     :1642-1658): level l = the input feature map average-pooled l times, `repeats` FluidLayers, bicubic back to the input
     size; concat of the levels with the raw inputs.  The reference re-pools the feature map from scratch for every level; the
     values are identical to pooling the previous level once more, which is what the graph does.  Returns (builder, tensor id
     of the concat).  Any c_h with learned padding (the run list's configurations, pinned by the reference goldens); with fixed
     padding c_h must stay a multiple of 8.  spectral: every FluidLayer of the trunk is a SpectralFluidLayer (:1211-1254,
-    :1535-1570); the heads stay what they are."""
+    :1535-1570); the heads stay what they are.  drop_rate: every (non-spectral) FluidLayer of the trunk ends in dropout
+    (:1218, :1252); the heads have none."""
     learned = r_p == "learned"
     if c_h % 8 and not learned:
         raise NotImplementedError("the HIP path of NewFluidNet / FluidNet with fixed padding needs c_h to be a multiple of 8 "
                                   "(r_p='learned' takes any c_h)")
     b = _Builder(c_i, f, use_symm, learned)
-    x_in = b.fluid("conv.0.", [0], c_h, spectral=spectral).out
+    x_in = b.fluid("conv.0.", [0], c_h, spectral=spectral, drop=drop_rate).out
     pooled = x_in
     outs = []
     for l in range(levels):
@@ -273,7 +285,7 @@ def _fluid_trunk(levels, c_i, c_h, *, r_p, use_symm, repeats, f, factor, spectra
             pooled = p
         cur = pooled
         for r in range(repeats):
-            cur = b.fluid(f"convs.{l}.{r}.", [cur], c_h, spectral=spectral).out
+            cur = b.fluid(f"convs.{l}.{r}.", [cur], c_h, spectral=spectral, drop=drop_rate).out
         if l > 0:
             up = b.new(c_h)
             b.nodes.append(UpNode(cur, up, like=x_in))
@@ -295,38 +307,47 @@ def _fluid_head(b, cat, c_h, c_o, *, act, r_p, **first) -> NetGraph:
     return NetGraph(c_i, c_o, b.ch, b.nodes, subtract_mean=True, pad_mode="zeros" if b.learned else r_p, act=act, divisor=1)
 
 
-def newfluidnet_graph(levels, c_i, c_h, c_o, *, act, r_p, use_symm, repeats, f, factor=2, spectral=False) -> NetGraph:
+def newfluidnet_graph(levels, c_i, c_h, c_o, *, act, r_p, use_symm, repeats, f, factor=2, spectral=False, drop_rate=0.0) -> NetGraph:
     """Layer wiring of NewFluidNet.__init__/forward (reference pytorch_networks_convae.py:1215-1346): the shared trunk
     (_fluid_trunk), then the head (_fluid_head)."""
-    b, cat = _fluid_trunk(levels, c_i, c_h, r_p=r_p, use_symm=use_symm, repeats=repeats, f=f, factor=factor, spectral=spectral)
+    b, cat = _fluid_trunk(levels, c_i, c_h, r_p=r_p, use_symm=use_symm, repeats=repeats, f=f, factor=factor, spectral=spectral,
+                          drop_rate=drop_rate)
     return _fluid_head(b, cat, c_h, c_o, act=act, r_p=r_p)
 
 
-def fluidnet_graph(levels, c_i, c_h, c_o, *, act, r_p, use_symm, repeats, f, factor=2, spectral=False) -> NetGraph:
+def fluidnet_graph(levels, c_i, c_h, c_o, *, act, r_p, use_symm, repeats, f, factor=2, spectral=False, drop_rate=0.0) -> NetGraph:
     """Layer wiring of FluidNet.__init__/forward with loss_type 'curl' (reference pytorch_networks_convae.py:1581-1665): the
     trunk of NewFluidNet, then a head whose first conv grows the field by one pixel on every side, so that the output is
     (H + 2) x (W + 2) and the curl head's centred differences land on H x W (mc_curl_valid_*).  Learned padding: conv.1 is a
     k = f BoundaryLearnedConvolution2D called with bc_x = bc_y = 2 (:1660), conv.2 / conv.3 plain learned convs.  Fixed
     padding: conv.1 is the constructor's 3 x 3 conv with padding (2, 2), conv.2 / conv.3 3 x 3 with padding 1 (the reference's
     forward passes bc_x / bc_y to that nn.Conv2d and fails)."""
-    b, cat = _fluid_trunk(levels, c_i, c_h, r_p=r_p, use_symm=use_symm, repeats=repeats, f=f, factor=factor, spectral=spectral)
+    b, cat = _fluid_trunk(levels, c_i, c_h, r_p=r_p, use_symm=use_symm, repeats=repeats, f=f, factor=factor, spectral=spectral,
+                          drop_rate=drop_rate)
     return _fluid_head(b, cat, c_h, c_o, act=act, r_p=r_p, **(dict(bc_x=2, bc_y=2) if b.learned else dict(pad=2)))
 
 
 def single_layer_graph(c_in, c_out, k, pad, pad_mode, sym_h, post, act, groups, gn: bool, learned: bool = False,
                        sym_v: int = 0, sym_hv: int = 0, bc_x: int = 1, bc_y: int = 1, input_grad: bool = False,
-                       spectral: bool = False) -> NetGraph:
+                       spectral: bool = False, drop_rate: float = 0.0) -> NetGraph:
     """One conv (+GN+act): SymmetricConv2d / FluidLayer / BoundaryLearnedConvolution2D (learned; bc_x, bc_y as in its forward)
     / SpectralConv2d / SpectralFluidLayer (spectral; k, pad, sym are ignored) used stand-alone.  input_grad (learned and
-    spectral layers): backward leaves d(loss)/d(input) in Engine.input_grad_cb8()."""
+    spectral layers): backward leaves d(loss)/d(input) in Engine.input_grad_cb8().  drop_rate: dropout after the activation
+    (FluidLayer; a spectral layer ignores it)."""
     if input_grad and not (learned or spectral):
         raise NotImplementedError("input_grad is implemented for learned-padding and spectral layers")
     ch = {0: c_in, 1: c_out}
     if spectral:
-        node = ConvNode("layers.0." if gn else "", [0], 1, c_out, 0, 0, 0, post, "layers.1." if gn else None, groups, spectral=True)
+        node = ConvNode("layers.0." if gn else "", [0], 1, c_out, 0, 0, 0, post, "layers.1." if gn else None, groups, spectral=True,
+                        layer=0)
         return NetGraph(c_in, c_out, ch, [node], pad_mode="zeros", act=act, input_grad=input_grad)
     node = ConvNode("layers.0." if gn else "", [0], 1, c_out, k, pad, sym_h, post, "layers.1." if gn else None, groups,
-                    learned=learned, sym_v=sym_v, sym_hv=sym_hv, bc_x=bc_x, bc_y=bc_y)
+                    learned=learned, sym_v=sym_v, sym_hv=sym_hv, bc_x=bc_x, bc_y=bc_y, layer=0)
+    if drop_rate:
+        L.dropout_keep16(drop_rate)
+        if post != L.POST_GN_ACT:
+            raise NotImplementedError("dropout follows GroupNorm + activation (a FluidLayer)")
+        node.drop = float(drop_rate)
     return NetGraph(c_in, c_out, ch, [node], pad_mode=pad_mode, act=act, input_grad=input_grad)
 
 
@@ -544,6 +565,39 @@ class Engine:
         # forward; reduce + finalize + apply backward).  MI355X, CFG-3: 64 x 64 and 32 x 32 layers 21 -> 11 us forward and
         # 38 -> 24 us backward; 128 x 128 layers break even (25 -> 24, 49 -> 53 us: 128 blocks do not fill the chip)
         self.gn_small_pix = int(os.environ.get("MANTLE_GN_SMALL_PIX", str(64 * 64 + 4)))
+        # dropout (graphs with drop nodes only): the device state (seed_lo, seed_hi, step, 0) is allocated in configure();
+        # the seed is kept here so that it survives a re-plan
+        self.has_drop = any(n.kind == "conv" and n.drop > 0 for n in graph.nodes)
+        self.drop_state = None
+        self._drop_seed = 0
+        self._drop_on = False                # whether the last forward ran with dropout (its backward follows it)
+
+    # -------------------------------------------------------------- dropout state
+    def set_dropout_seed(self, seed: int):
+        """64-bit seed of the dropout masks (low / high word = the Philox key); resets the step counter to 0."""
+        self._drop_seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self._write_drop_state(0)
+
+    def _write_drop_state(self, step: int):
+        if self.drop_state is not None:
+            host = np.array([self._drop_seed & 0xFFFFFFFF, self._drop_seed >> 32, int(step) & 0xFFFFFFFF, 0], dtype=np.uint32)
+            self.drop_state.copy_(torch.from_numpy(host.view(np.int32)))
+
+    def dropout_step(self) -> int:
+        """The device step counter: the number of training-mode forwards since the seed was set (host sync)."""
+        if self.drop_state is None:
+            return 0
+        return int(self.drop_state[2].item()) & 0xFFFFFFFF
+
+    def set_dropout_step(self, step: int):
+        """Rewind / set the step counter (the trainer restores it after the warm-up pass of a graph capture)."""
+        self._write_drop_state(step)
+
+    def _drop_desc(self, node):
+        """mc_dropout of a node in a dropout pass, else None."""
+        if not (self._drop_on and node.drop > 0):
+            return None
+        return L.Dropout(L.ptr(self.drop_state), node.layer, L.dropout_keep16(node.drop))
 
     # -------------------------------------------------------------- planning
     def freeze(self):
@@ -641,6 +695,9 @@ class Engine:
         self.dOut = None if self.final_plain else cb8g(fo.C, fo.H, fo.W)
         self.chan_mean = torch.empty((N, g.c_out), **f32) if g.subtract_mean else None
         self.gmean = torch.empty((N, g.c_out), **f32) if g.subtract_mean else None
+        if self.has_drop:
+            self.drop_state = torch.zeros(4, dtype=torch.int32, device=device)
+            self._write_drop_state(0)
         self.shape = (N, H, W, str(device))
 
     def _plan_gn(self, e, node, o, f32):
@@ -671,7 +728,7 @@ class Engine:
         cons = self.cons[node.out]
         fusable = all(c.kind == "up" or (c.kind == "conv" and not c.learned and not c.spectral) for c in cons)
         o.fused = bool((self.fuse & 1) and node.post != L.POST_NONE and fusable and (cons or node.pool > 1)
-                       and ho * wo <= self.fuse_maxpix)
+                       and ho * wo <= self.fuse_maxpix and not node.drop)      # (a dropout layer's output is materialised)
         if o.fused:
             o.raw, o.act = e["Y"], L.ACTS[g.act]
         elif node.post != L.POST_NONE:
@@ -699,7 +756,8 @@ class Engine:
                     and L.load().mc_conv_kernel_name(C.byref(dd)).decode().startswith("k_conv_rr")):
                 dz_here = True
             if (dz_here and len(srcs) == 1 and pe is not None and pe["node"].post != L.POST_NONE
-                    and not pe["node"].learned and not pe["node"].spectral and len(self.cons[node.srcs[0]]) == 1 and pe["node"].pool == 1):
+                    and not pe["node"].learned and not pe["node"].spectral and len(self.cons[node.srcs[0]]) == 1 and pe["node"].pool == 1
+                    and not pe["node"].drop):       # (the epilogue's dz = dA act'(z) knows no mask)
                 dtiles = L.call("mc_conv_tiles", C.byref(dd))
                 fblocks = L.call("mc_fold_blocks", h, w, node.pad, self.mode)
                 e["epi"] = pe
@@ -868,10 +926,13 @@ class Engine:
             return None
         return fo.buf, (self.chan_mean if self.g.subtract_mean else None), self.g.crop_w, (self.N, self.g.c_out, self.out_h, self.out_w)
 
-    def forward(self, x: torch.Tensor, params: Dict[str, torch.Tensor], chan_scale=None, out=None, unpack=True) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, params: Dict[str, torch.Tensor], chan_scale=None, out=None, unpack=True,
+                drop=False) -> torch.Tensor:
         """x: [N, >= c_in, H, W] f32 device tensor (extra trailing channels are ignored)
         -> [N, c_out, H', W'] f32.  chan_scale: optional [c_in] f32 per-channel input scale.  out: optional preallocated
-        result (the fused trainer passes one so that a captured step allocates nothing)."""
+        result (the fused trainer passes one so that a captured step allocates nothing).  drop: training mode -- the
+        graph's dropout layers are active, and the device step counter advances first (a one-thread kernel on the stream,
+        so every replay of a captured step draws a new mask); graphs without dropout layers ignore it."""
         L.require_cuda(x, "network input")
         if x.dtype != torch.float32:
             x = x.float()
@@ -883,6 +944,9 @@ class Engine:
         st = L.stream()
         g, T = self.g, self.T
         act = L.ACTS[g.act]
+        self._drop_on = bool(drop) and self.has_drop
+        if self._drop_on:
+            L.call("mc_dropout_advance", L.ptr(self.drop_state), st)
         L.call("mc_pack_nchw", L.ptr(x), N, g.c_in, Ci, H, W, g.in_pad_w, self.mode, L.ptr(chan_scale), self.mc_dtype,
                L.ptr(T[0].buf), st)
         self._pack_all_banks(params, st)
@@ -934,8 +998,10 @@ class Engine:
             if small:
                 # statistics + activation (+ pooling) of a small layer in one launch
                 pooled = T[node.pooled].buf if node.pool > 1 else None
-                L.call("mc_gn_act_fwd_small", L.ptr(e["Y"]), L.ptr(e["part"]), e["tiles"], N, node.c_out, o.H, o.W, node.groups, 1e-5,
-                       L.ptr(gamma), L.ptr(beta), act, node.pool, self.mc_dtype, L.ptr(e["stats"]), L.ptr(o.buf), L.ptr(pooled), st)
+                dr = self._drop_desc(node)
+                L.call("mc_gn_act_fwd_small" + ("_drop" if dr else ""), L.ptr(e["Y"]), L.ptr(e["part"]), e["tiles"], N, node.c_out,
+                       o.H, o.W, node.groups, 1e-5, L.ptr(gamma), L.ptr(beta), act, node.pool, self.mc_dtype, L.ptr(e["stats"]),
+                       L.ptr(o.buf), L.ptr(pooled), *((C.byref(dr),) if dr else ()), st)
                 continue
             if node.post == L.POST_GN_ACT:
                 # (mean, rstd) per (sample, group) + the (scale, shift, mean, rstd) table consumers normalise on load with
@@ -948,9 +1014,10 @@ class Engine:
                            L.ptr(T[node.pooled].buf), st)
             elif not final:
                 pooled = T[node.pooled].buf if node.pool > 1 else None
-                L.call("mc_gn_act_fwd", L.ptr(e["Y"]), N, node.c_out, o.H, o.W, node.groups,
+                dr = self._drop_desc(node)
+                L.call("mc_gn_act_fwd" + ("_drop" if dr else ""), L.ptr(e["Y"]), N, node.c_out, o.H, o.W, node.groups,
                        L.ptr(e.get("stats")), L.ptr(gamma), L.ptr(beta), node.post, act, node.pool, self.mc_dtype,
-                       L.ptr(o.buf), L.ptr(pooled), st)
+                       L.ptr(o.buf), L.ptr(pooled), *((C.byref(dr),) if dr else ()), st)
             elif g.subtract_mean:
                 L.call("mc_gn_finalize", L.ptr(e["part"]), N, e["tiles"], node.c_out, 1, o.H * o.W, 1e-5, None,
                        L.ptr(self.chan_mean), st)
@@ -1099,22 +1166,24 @@ class Engine:
                 g1 = C.byref(gs[1]) if len(gs) > 1 else None
                 gamma = self._param(params, node.gn_name + "weight") if node.gn_name else None
                 beta = self._param(params, node.gn_name + "bias") if node.gn_name else None
+                dr = self._drop_desc(node)           # the forward's mask, regenerated from the same (seed, step, layer)
+                sfx, dra = ("_drop", (C.byref(dr),)) if dr else ("", ())
                 if node.post == L.POST_GN_ACT and "pc" in e:
-                    L.call("mc_gn_act_bwd_small", L.ptr(e["Y"]), N, node.c_out, o.H, o.W, node.groups, L.ptr(e["stats"]),
-                           L.ptr(gamma), L.ptr(beta), act, self.mc_dtype, g0, g1, L.ptr(dY), L.ptr(e["pc"]), st)
+                    L.call("mc_gn_act_bwd_small" + sfx, L.ptr(e["Y"]), N, node.c_out, o.H, o.W, node.groups, L.ptr(e["stats"]),
+                           L.ptr(gamma), L.ptr(beta), act, self.mc_dtype, g0, g1, L.ptr(dY), L.ptr(e["pc"]), *dra, st)
                     gp_jobs.append((L.ptr(e["pc"]), node.c_out, L.ptr(grads[node.gn_name + "weight"]),
                                     L.ptr(grads[node.gn_name + "bias"])))
                 else:
                     if node.post == L.POST_GN_ACT:
-                        L.call("mc_gn_act_bwd_reduce", L.ptr(e["Y"]), N, node.c_out, o.H, o.W, node.groups,
+                        L.call("mc_gn_act_bwd_reduce" + sfx, L.ptr(e["Y"]), N, node.c_out, o.H, o.W, node.groups,
                                L.ptr(e["stats"]), L.ptr(gamma), L.ptr(beta), node.post, act, self.mc_dtype, g0, g1,
-                               L.ptr(e["gpart"]), st)
+                               L.ptr(e["gpart"]), *dra, st)
                         L.call("mc_gn_act_bwd_finalize", L.ptr(e["gpart"]), N, e["gblocks"], node.c_out, node.groups,
                                o.H * o.W, L.ptr(gamma), L.ptr(e["m12"]), L.ptr(grads[node.gn_name + "weight"]),
                                L.ptr(grads[node.gn_name + "bias"]), st)
-                    L.call("mc_gn_act_bwd_apply", L.ptr(e["Y"]), N, node.c_out, o.H, o.W, node.groups,
+                    L.call("mc_gn_act_bwd_apply" + sfx, L.ptr(e["Y"]), N, node.c_out, o.H, o.W, node.groups,
                            L.ptr(e.get("stats")), L.ptr(e.get("m12")), L.ptr(gamma), L.ptr(beta), node.post, act,
-                           self.mc_dtype, g0, g1, L.ptr(dY), st)
+                           self.mc_dtype, g0, g1, L.ptr(dY), *dra, st)
             if node.learned:
                 self._learned_backward(e, srcs[0], dY, params, grads, st)
                 continue

@@ -22,7 +22,7 @@ class _NetFunction(torch.autograd.Function):
     def forward(ctx, mod, x, *plist):
         eng = mod.engine()
         params = mod._param_dict(plist)
-        out = eng.forward(x, params, getattr(mod, "_chan_scale", None))
+        out = eng.forward(x, params, getattr(mod, "_chan_scale", None), drop=mod._drop_next)
         mod._fwd_version += 1
         ctx.mod, ctx.params, ctx.version = mod, params, mod._fwd_version
         ctx.dtypes = [p.dtype for p in plist]
@@ -59,6 +59,7 @@ class HipNetMixin:
         self._precision = precision or getattr(self, "_precision", None) or DEFAULT_PRECISION   # (keeps an earlier set_precision)
         self._engines: Dict[str, Engine] = {}
         self._fwd_version = 0
+        self._drop_seed = getattr(self, "_drop_seed", None)
         self._pnames: List[str] = []
 
     @property
@@ -77,7 +78,16 @@ class HipNetMixin:
         e = self._engines.get(self._precision)
         if e is None:
             e = self._engines[self._precision] = Engine(self._graph, self._precision)
+            e.set_dropout_seed(torch.initial_seed() if self._drop_seed is None else self._drop_seed)
         return e
+
+    def set_dropout_seed(self, seed: int):
+        """Seed of the dropout masks (64 bits) for every engine of this module, present and future; the step counter
+        restarts at 0.  The mask of a training-mode forward is a pure function of (seed, step, layer, element)."""
+        self._drop_seed = int(seed)
+        for e in self._engines.values():
+            e.set_dropout_seed(self._drop_seed)
+        return self
 
     def _named_hip_params(self):
         return list(self.named_parameters())
@@ -99,6 +109,9 @@ class HipNetMixin:
         self._pnames = [n for n, _ in named]
         for n, p in named:
             L.require_cuda(p, f"parameter {n}")
+        # dropout follows module.training, as nn.Dropout does, except under torch.no_grad(): a forward that cannot be trained
+        # through (validation, rollout) is the deterministic network
+        self._drop_next = bool(self.training) and torch.is_grad_enabled()
         return _NetFunction.apply(self, x, *[p for _, p in named])
 
 

@@ -91,13 +91,20 @@ GSUM_FROM_LOSS = os.environ.get("MANTLE_GSUM_FROM_LOSS", "1") != "0"   # spatial
 CB8_LOSS = os.environ.get("MANTLE_CB8_LOSS", "1") != "0"     # the fused loss reads the network output in its CB8 layout (no NCHW copy)
 
 
+def dropout_seed(seed: int, rank: int = 0, epoch: int = 0) -> int:
+    """64-bit seed of a rank's dropout masks: low word seed + rank (DDP ranks draw different masks), high word the start
+    epoch (a restarted run does not replay epoch 0's masks)."""
+    return ((int(epoch) & 0xFFFFFFFF) << 32) | ((int(seed) + int(rank)) & 0xFFFFFFFF)
+
+
 class Trainer:
     _promotion_logged = False
 
     def __init__(self, model_uvp: torch.nn.Module, model_AD, train_data, cv_data, train_data_init, cv_data_init,
                  optimizer: torch.optim.Optimizer, scheduler, gpu_id: int, save_every: int, nn_dir, p_pred=False,
                  debug=False, network="fluidnet", loss_scale=False, loss_derivative=False, roll_forward=1, epoch=0,
-                 loss_type="curl", *, norm="l1", lambda_mom=0.0, precision=None, use_graph=False, log_every=100):
+                 loss_type="curl", *, norm="l1", lambda_mom=0.0, precision=None, use_graph=False, log_every=100,
+                 drop_seed=None):
         if network not in ("unet", "iunet", "convae", "newfluidnet", "fluidnet", "ifluidnet"):
             raise NotImplementedError(f"network={network!r}: the HIP path covers 'unet' / 'iunet', 'convae', 'newfluidnet' and "
                                       "'fluidnet' / 'ifluidnet'")
@@ -137,6 +144,11 @@ class Trainer:
         self._lr_host = None
         broadcast_flat(self.flat.param)
         self.world = dist.get_world_size() if (dist.is_available() and dist.is_initialized()) else 1
+        # dropout masks (models built with drop_rate > 0): train_step draws them, eval_step / get_loss under no_grad do not
+        rank = dist.get_rank() if self.world > 1 else 0
+        self.drop_seed = dropout_seed(torch.initial_seed() if drop_seed is None else drop_seed, rank, epoch)
+        if hasattr(self.model_uvp, "set_dropout_seed"):
+            self.model_uvp.set_dropout_seed(self.drop_seed)
         a_bound = getattr(self.model_uvp, "a_bound", 10.0)
         self.loss = StokesLoss(p_pred if network != "convae" else False,
                                loss_type if network != "convae" else "mae", loss_scale, loss_derivative, norm=norm,
@@ -271,7 +283,7 @@ class Trainer:
             gVTp = self._roll_chain(gVTp, paras, lambda x: eng.forward(x, params, self.chan_scale, out=ybuf))
         # (one-launch loss: it reads the last convolution's output where it lies, and forward() returns None instead of an
         # NCHW copy when the head ends in an f32 CB8 tensor)
-        y = eng.forward(gVTp, params, self.chan_scale, out=ybuf, unpack=not (loss.fusable() and CB8_LOSS))
+        y = eng.forward(gVTp, params, self.chan_scale, out=ybuf, unpack=not (loss.fusable() and CB8_LOSS), drop=train)
         if y is None:
             out8, gy = loss.evaluate(None, uvp, yc, paras, scaler, cb8=eng.output_cb8())
         else:
@@ -326,10 +338,13 @@ class Trainer:
             self._static = st
             side = torch.cuda.Stream(device=self.device)
             side.wait_stream(torch.cuda.current_stream())
+            eng = self.model_uvp.engine()
+            drop_step = eng.dropout_step()          # (0 before the engine is planned)
             with torch.cuda.stream(side):           # warm-up: allocates every engine buffer outside the capture
                 self._fwd_bwd(st["gVTp"], st["uvp"], st["yc"], st["paras"], st["scaler"], train=True)
             torch.cuda.current_stream().wait_stream(side)
             torch.cuda.synchronize(self.device)
+            eng.set_dropout_step(drop_step)         # the warm-up consumes no dropout step: eager and captured runs see 1, 2, 3, ...
             # with a process group alive its watchdog thread polls events while we capture: only calls of THIS thread may
             # invalidate the capture (the default "global" mode would turn the watchdog's event query into a capture error)
             mode = dict(capture_error_mode="thread_local") if (dist.is_available() and dist.is_initialized()) else {}

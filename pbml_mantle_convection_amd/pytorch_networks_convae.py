@@ -136,7 +136,7 @@ def pad_uvp(u, v, p=None):
 # --------------------------------------------------------------------------------------------------
 # FluidLayer (reference :702-799): conv -> GroupNorm -> activation -> dropout(p)
 # --------------------------------------------------------------------------------------------------
-def _check_common(act_fn, r_p, dilation, drop_rate=0.0, spectral_conv=False, blurr=False, spectral_ok=False):
+def _check_common(act_fn, r_p, dilation, drop_rate=0.0, spectral_conv=False, blurr=False, spectral_ok=False, drop_ok=False):
     if act_fn not in _SUPPORTED_ACTS:
         raise NotImplementedError(f"act_fn={act_fn!r}: supported on the HIP path: {_SUPPORTED_ACTS} "
                                   "('sine' is undefined in the reference itself)")
@@ -144,8 +144,12 @@ def _check_common(act_fn, r_p, dilation, drop_rate=0.0, spectral_conv=False, blu
         raise NotImplementedError(f"r_p={r_p!r}: the HIP path implements zeros / replicate / reflect / learned padding")
     if dilation != 1:
         raise NotImplementedError("dilation != 1 is not implemented on the HIP path")
-    if drop_rate not in (0, 0.0):
-        raise NotImplementedError("dropout with p > 0 is not implemented on the HIP path (reference default 0)")
+    if drop_ok:
+        if not 0.0 <= drop_rate < 1.0:
+            raise ValueError(f"drop_rate must satisfy 0 <= p < 1, got {drop_rate}")
+    elif drop_rate not in (0, 0.0):
+        raise NotImplementedError("dropout with p > 0 is built for FluidLayer, NewFluidNet and FluidNet (not for the Unet's "
+                                  "pooled layers; reference default 0)")
     if spectral_conv and not spectral_ok:
         raise NotImplementedError("spectral_conv is built for NewFluidNet and FluidNet (the Unet's spectral layers are not)")
     if blurr:
@@ -156,9 +160,12 @@ class FluidLayer(nn.Module, HipNetMixin):
     def __init__(self, c_i: int, c_o: int, act_fn: str = "selu", r_p="zeros", use_symm=False, dilation=1, f=3,
                  drop_rate=0.0):
         super().__init__()
-        _check_common(act_fn, r_p, dilation, drop_rate)
+        _check_common(act_fn, r_p, dilation, drop_rate, drop_ok=True)
         self.r_p = "constant" if r_p == "zeros" else r_p
         self.act_fn = act_fn
+        # (reference :753; the engine applies it inside the GroupNorm / activation kernels in training mode.  The rate is
+        # quantised to 2^-16: an element is kept with probability round((1 - p) 65536) / 65536)
+        self.dropout = torch.nn.Dropout(drop_rate)
         self.layers = nn.ModuleList()
         h_s = fluid_sym_h(c_o)
         if r_p == "learned":
@@ -172,7 +179,7 @@ class FluidLayer(nn.Module, HipNetMixin):
         self.layers.append(torch.nn.GroupNorm(fluid_groups(c_o), c_o))
         self._init_hipnet(single_layer_graph(c_i, c_o, f, f // 2, "zeros" if r_p == "learned" else r_p,
                                              h_s if use_symm else 0, L.POST_GN_ACT, act_fn, fluid_groups(c_o), gn=True,
-                                             learned=(r_p == "learned")))
+                                             learned=(r_p == "learned"), input_grad=(r_p == "learned"), drop_rate=drop_rate))
 
     def forward(self, inputs, bc_x=1, bc_y=1):
         if self.r_p == "learned" and (bc_x != 1 or bc_y != 1):
@@ -365,14 +372,14 @@ class NewFluidNet(nn.Module, HipNetMixin):
                  loss_type="mae", use_symm=False, dilation=1, a_bound=4.0, use_cosine=False, repeats=3, use_skip=False,
                  f=3, p_pred=True, spectral_conv=False, blurr=False, drop_rate=0.0, factor=2):
         super().__init__()
-        _check_common(act_fn, r_p, dilation, drop_rate, spectral_conv, blurr, spectral_ok=True)
+        _check_common(act_fn, r_p, dilation, drop_rate, spectral_conv, blurr, spectral_ok=True, drop_ok=True)
         self.levels, self.loss_type, self.a_bound = levels, loss_type, a_bound
         self.use_cosine, self.repeats, self.use_skip, self.p_pred = use_cosine, repeats, use_skip, p_pred
         self.c_h, self.c_i, self.c_o = c_h, c_i, c_o
         self.blurrer = None
         self.r_p = "constant" if r_p == "zeros" else r_p
         graph = newfluidnet_graph(levels, c_i, c_h, c_o, act=act_fn, r_p=r_p, use_symm=use_symm, repeats=repeats, f=f,
-                                  factor=factor, spectral=spectral_conv)
+                                  factor=factor, spectral=spectral_conv, drop_rate=drop_rate)
 
         def fl(cin, cout):
             if spectral_conv:                                                  # reference :1211-1254
@@ -462,7 +469,7 @@ class FluidNet(nn.Module, HipNetMixin):
                  loss_type="mae", use_symm=False, dilation=1, a_bound=4.0, use_cosine=False, repeats=3, use_skip=False,
                  f=3, p_pred=True, spectral_conv=False, blurr=False, drop_rate=0.0, factor=2):
         super().__init__()
-        _check_common(act_fn, r_p, dilation, drop_rate, spectral_conv, blurr, spectral_ok=True)
+        _check_common(act_fn, r_p, dilation, drop_rate, spectral_conv, blurr, spectral_ok=True, drop_ok=True)
         if loss_type in ("mae", "mass"):
             raise NotImplementedError(f"FluidNet with loss_type={loss_type!r} fails in the reference (its forward skips conv.1, so "
                                       "GroupNorm sees c_h * levels + c_i channels); only 'curl' is built")
@@ -483,7 +490,7 @@ class FluidNet(nn.Module, HipNetMixin):
         self.r_p = "constant" if r_p == "zeros" else r_p
         self.act = {"selu": nn.SELU, "tanh": nn.Tanh, "elu": nn.ELU, "silu": nn.SiLU, "relu": nn.ReLU, "gelu": nn.GELU}[act_fn]()
         graph = fluidnet_graph(levels, c_i, c_h, c_o, act=act_fn, r_p=r_p, use_symm=use_symm, repeats=repeats, f=f,
-                               factor=factor, spectral=spectral_conv)
+                               factor=factor, spectral=spectral_conv, drop_rate=drop_rate)
 
         def fl(cin, cout):
             if spectral_conv:                                                  # reference :1535-1570
