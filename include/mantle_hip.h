@@ -582,6 +582,43 @@ int mc_adam_step_flat(float* param, const float* grad, float* exp_avg, float* ex
                       const float* lr_dev, float beta1, float beta2, float eps, float weight_decay,
                       float grad_scale, int32_t* step_count_dev, void* stream);
 
+/* ---- guarded Adam step: global-norm clipping and non-finite step skipping ---------------------- */
+/* Device record of the last mc_grad_guard_eval call.  32 bytes, caller-owned, zeroed once by the caller. */
+typedef struct {
+  float    norm;        /* || grad_scale * g ||_2 of the last call (f32 rounding of the f64 value; may be +inf; not finite
+                           when nonfinite > 0) */
+  float    coef;        /* factor applied to the gradient by the last call (1 when not clipping) */
+  uint32_t nonfinite;   /* elements of g that were not finite in the last call (saturating) */
+  uint32_t skip;        /* 1: the last step was skipped */
+  uint32_t skipped;     /* steps skipped since the record was zeroed */
+  uint32_t consecutive; /* steps skipped in a row up to and including the last call */
+  uint32_t pad[2];
+} mc_grad_guard;
+
+/* Number of partial slots the workspace of mc_grad_guard_eval needs (host only, no GPU): one per 256 float4 of the
+ * buffer: at least 1, non-decreasing, at most 1024; 0 for numel <= 0. */
+int mc_grad_norm_blocks(int64_t numel);
+/* Two launches, no atomics, every sum in a fixed order: the record is bit-reproducible.
+ *   1. per block, sum g^2 and the count of non-finite g, both accumulated in f64 -> ws[b], ws[blocks + b] (plain stores);
+ *   2. one block adds the partials in a fixed order (a tree of fixed shape) and writes the record:
+ *        norm64 = grad_scale * sqrt(sum g^2), norm = (float)norm64;
+ *        coef   = max_norm > 0 ? min(1, max_norm / (norm64 + 1e-6)) : 1, in f64, stored as f32 (clip_grad_norm_'s formula);
+ *                 1 whenever nonfinite > 0;
+ *        skip   = skip_nonfinite && nonfinite > 0;
+ *      and increments *step_count_dev only when skip == 0 (a skipped step does not advance Adam's t); skipped and
+ *      consecutive count the skipped steps, consecutive returns to 0 with the first step taken.
+ * ws: [2 * mc_grad_norm_blocks(numel)] doubles; grad 16-byte aligned.  MC_EINVAL (nothing launched) for a null pointer,
+ * numel <= 0, a misaligned buffer, max_norm < 0 or NaN.  The library allocates nothing. */
+int mc_grad_guard_eval(const float* grad, int64_t numel, float grad_scale, float max_norm, int32_t skip_nonfinite,
+                       double* ws, mc_grad_guard* guard, int32_t* step_count_dev, void* stream);
+/* mc_adam_step_flat after mc_grad_guard_eval, one launch: stores nothing when guard->skip is set; otherwise mc_adam_step_flat's
+ * arithmetic with gs = grad_scale * guard->coef (one f32 product) in place of grad_scale, i.e. the clip acts on the scaled
+ * raw gradient and weight_decay * p is added after it (clip_grad_norm_ followed by torch.optim.Adam).  It does NOT touch
+ * step_count_dev: mc_grad_guard_eval has. */
+int mc_adam_step_flat_guarded(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t numel,
+                              const float* lr_dev, float beta1, float beta2, float eps, float weight_decay,
+                              float grad_scale, int32_t* step_count_dev, const mc_grad_guard* guard, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -64,6 +64,21 @@ def dropout_keep16(p: float) -> int:
     return min(max(int(round((1.0 - p) * 65536.0)), 1), 65535)
 
 
+class GradGuard(C.Structure):
+    """mc_grad_guard: the device record of the guarded optimizer step (32 bytes)."""
+    _fields_ = [("norm", C.c_float), ("coef", C.c_float), ("nonfinite", C.c_uint32), ("skip", C.c_uint32),
+                ("skipped", C.c_uint32), ("consecutive", C.c_uint32), ("pad", C.c_uint32 * 2)]
+
+
+GRAD_GUARD_WORDS = C.sizeof(GradGuard) // 4      # the record as an int32 device tensor
+
+
+def read_grad_guard(t):
+    """The mc_grad_guard record held by the int32 device tensor t as a dict (one device-to-host copy)."""
+    rec = GradGuard.from_buffer_copy(t.cpu().numpy().tobytes())
+    return {k: getattr(rec, k) for k in ("norm", "coef", "nonfinite", "skip", "skipped", "consecutive")}
+
+
 class LossDesc(C.Structure):
     _fields_ = [("n", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("p_pred", C.c_int32),
                 ("loss_type", C.c_int32), ("loss_scale", C.c_int32), ("loss_derivative", C.c_int32),
@@ -184,13 +199,16 @@ SIGNATURES = {
     "mc_spectral_mix_fwd": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "mc_spectral_mix_bwd": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mc_adam_step_flat": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _f32, _f32, _f32, _f32, _f32, _vp, _vp]),
+    "mc_grad_norm_blocks": (C.c_int, [_i64]),
+    "mc_grad_guard_eval": (C.c_int, [_vp, _i64, _f32, _f32, _i32, _vp, _vp, _vp, _vp]),
+    "mc_adam_step_flat_guarded": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _f32, _f32, _f32, _f32, _f32, _vp, _vp, _vp]),
 }
 
 # entry points whose return value is a quantity, not a status code
 VALUE_RETURNING = {"mc_version", "mc_strerror", "mc_conv_kernel_name", "mc_packed_weight_bytes", "mc_conv_bank_read_extent", "mc_conv_tiles",
                    "mc_wgrad_partial_bytes", "mc_gn_bwd_blocks",
                    "mc_learned_validate", "mc_learned_bank_bytes", "mc_learned_wgrad_workspace_bytes", "mc_fold_blocks", "mc_loss_fused_blocks",
-                   "mc_spectral_slots", "mc_philox4x32"}
+                   "mc_spectral_slots", "mc_philox4x32", "mc_grad_norm_blocks"}
 
 _lib = None
 

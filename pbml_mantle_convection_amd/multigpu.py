@@ -104,7 +104,7 @@ class Trainer:
                  optimizer: torch.optim.Optimizer, scheduler, gpu_id: int, save_every: int, nn_dir, p_pred=False,
                  debug=False, network="fluidnet", loss_scale=False, loss_derivative=False, roll_forward=1, epoch=0,
                  loss_type="curl", *, norm="l1", lambda_mom=0.0, precision=None, use_graph=False, log_every=100,
-                 drop_seed=None):
+                 drop_seed=None, max_grad_norm: float = 0.0, skip_nonfinite: bool = False, max_skipped_in_a_row: int = 50):
         if network not in ("unet", "iunet", "convae", "newfluidnet", "fluidnet", "ifluidnet"):
             raise NotImplementedError(f"network={network!r}: the HIP path covers 'unet' / 'iunet', 'convae', 'newfluidnet' and "
                                       "'fluidnet' / 'ifluidnet'")
@@ -141,6 +141,18 @@ class Trainer:
         self.exp_avg_sq = torch.zeros_like(self.flat.param)
         self.step_count = torch.zeros(1, dtype=torch.int32, device=self.device)
         self.lr_dev = torch.zeros(1, dtype=torch.float32, device=self.device)
+        # guarded optimizer step (global-norm clip and / or skip on a non-finite gradient): the device record and the
+        # reduction's workspace exist only when a guard is on; with both off the step is the unguarded one
+        if not float(max_grad_norm) >= 0.0:
+            raise ValueError(f"max_grad_norm must be >= 0 (0 = no clipping), got {max_grad_norm}")
+        self.max_grad_norm, self.skip_nonfinite = float(max_grad_norm), bool(skip_nonfinite)
+        self.max_skipped_in_a_row = int(max_skipped_in_a_row)
+        self._guard = self._guard_ws = None
+        self._skipped_seen = 0
+        if self.max_grad_norm > 0.0 or self.skip_nonfinite:
+            self._guard = torch.zeros(L.GRAD_GUARD_WORDS, dtype=torch.int32, device=self.device)
+            self._guard_ws = torch.zeros(2 * L.call("mc_grad_norm_blocks", self.flat.numel), dtype=torch.float64,
+                                         device=self.device)
         self._lr_host = None
         broadcast_flat(self.flat.param)
         self.world = dist.get_world_size() if (dist.is_available() and dist.is_initialized()) else 1
@@ -314,9 +326,37 @@ class Trainer:
 
     def _optim_step(self):
         b1, b2, eps, wd = self._adam_args()
+        if self._guard is not None:
+            # ordered norm / non-finite reduction of the (all-reduced) flat gradient, then an Adam launch that honours it;
+            # the reduction's last launch advances step_count unless the step is skipped
+            L.call("mc_grad_guard_eval", L.ptr(self.flat.grad), self.flat.numel, 1.0 / self.world, self.max_grad_norm,
+                   int(self.skip_nonfinite), L.ptr(self._guard_ws), L.ptr(self._guard), L.ptr(self.step_count), L.stream())
+            L.call("mc_adam_step_flat_guarded", L.ptr(self.flat.param), L.ptr(self.flat.grad), L.ptr(self.exp_avg),
+                   L.ptr(self.exp_avg_sq), self.flat.numel, L.ptr(self.lr_dev), b1, b2, eps, wd, 1.0 / self.world,
+                   L.ptr(self.step_count), L.ptr(self._guard), L.stream())
+            return
         L.call("mc_adam_step_flat", L.ptr(self.flat.param), L.ptr(self.flat.grad), L.ptr(self.exp_avg),
                L.ptr(self.exp_avg_sq), self.flat.numel, L.ptr(self.lr_dev), b1, b2, eps, wd, 1.0 / self.world,
                L.ptr(self.step_count), L.stream())
+
+    def grad_guard(self):
+        """The guard record of the last optimizer step as a dict (norm, coef, nonfinite, skip, skipped, consecutive): one
+        device-to-host read, for logging and tests -- the training loop never calls it per step."""
+        if self._guard is None:
+            raise RuntimeError("no gradient guard: construct the Trainer with max_grad_norm > 0 or skip_nonfinite=True")
+        return L.read_grad_guard(self._guard)
+
+    def check_guard(self):
+        """Reads the record (one host sync) and stops a run that only skips: returns the record, None without a guard."""
+        if self._guard is None:
+            return None
+        rec = self.grad_guard()
+        if rec["consecutive"] >= self.max_skipped_in_a_row:
+            raise RuntimeError(f"{rec['consecutive']} optimizer steps in a row were skipped for non-finite gradients "
+                               f"({rec['nonfinite']} non-finite elements in the last one, limit max_skipped_in_a_row="
+                               f"{self.max_skipped_in_a_row}): the forward pass overflows; train with --precision bf16 or a "
+                               "lower learning rate")
+        return rec
 
     def train_step(self, gVTp, uvp, yc=None, paras=None, scaler=None):
         """zero_grad -> forward -> loss -> backward -> all-reduce -> Adam (reference _run_batch :307-320),
@@ -422,13 +462,16 @@ class Trainer:
         print(f"[GPU{self.gpu_id}] Epoch {epoch} | Steps: {len(self.train_data)}")
         acc = torch.zeros(8, dtype=torch.float64, device=self.device)
         i = -1
-        for i, data in enumerate(self.train_data):
-            t0 = time.time()
-            gVTp, uvp, scaler, paras, yc = self._unpack(data)
-            acc += self._run_batch(gVTp, uvp, scaler, True, paras=paras, yc=yc, sync=False).double()
-            if i % self.log_every == 0:                     # the only host sync in the hot loop
-                print(epoch, (acc[:6] / (i + 1)).tolist(), time.time() - t0)
-        self.losses = (acc[:6] / max(i + 1, 1)).tolist()
+        if self._guard is None:
+            for i, data in enumerate(self.train_data):
+                t0 = time.time()
+                gVTp, uvp, scaler, paras, yc = self._unpack(data)
+                acc += self._run_batch(gVTp, uvp, scaler, True, paras=paras, yc=yc, sync=False).double()
+                if i % self.log_every == 0:                     # the only host sync in the hot loop
+                    print(epoch, (acc[:6] / (i + 1)).tolist(), time.time() - t0)
+            self.losses = (acc[:6] / max(i + 1, 1)).tolist()
+        else:
+            self._run_train_guarded(epoch, acc)
         acc.zero_()
         i_cv = -1
         with torch.no_grad():
@@ -437,6 +480,30 @@ class Trainer:
                 gVTp, uvp, scaler, paras, yc = self._unpack(data)
                 acc += self._run_batch(gVTp, uvp, scaler, False, paras=paras, yc=yc, sync=False).double()
         self.losses_cv = (acc[:6] / max(i_cv + 1, 1)).tolist()
+
+    def _run_train_guarded(self, epoch, acc):
+        """The training half of _run_epoch with a guard on: a step's eight scalars enter the epoch's means only when all of
+        them are finite (decided and counted on the device), so one skipped batch does not turn them into NaN; the guard
+        record is read where the loop syncs anyway."""
+        cnt = torch.zeros((), dtype=torch.float64, device=self.device)
+        zero = torch.zeros(8, dtype=torch.float64, device=self.device)
+        i = -1
+        for i, data in enumerate(self.train_data):
+            t0 = time.time()
+            gVTp, uvp, scaler, paras, yc = self._unpack(data)
+            out8 = self._run_batch(gVTp, uvp, scaler, True, paras=paras, yc=yc, sync=False).double()
+            ok = torch.isfinite(out8).all()
+            acc += torch.where(ok, out8, zero)
+            cnt += ok
+            if i % self.log_every == 0:                     # the only host sync in the hot loop
+                print(epoch, (acc[:6] / cnt.clamp(min=1.0)).tolist(), time.time() - t0)
+                self.check_guard()
+        self.losses = (acc[:6] / cnt.clamp(min=1.0)).tolist()
+        rec = self.check_guard()
+        if rec["skipped"] > self._skipped_seen:
+            print(f"[mantle] epoch {epoch}: {rec['skipped'] - self._skipped_seen} of {i + 1} optimizer steps skipped for "
+                  f"non-finite gradients ({rec['skipped']} since the start)", flush=True)
+            self._skipped_seen = rec["skipped"]
 
     def _save_checkpoint(self, epoch):
         """File names, state_dict keys and the log line format of the reference (:412-436)."""
@@ -483,7 +550,7 @@ def build_model(network, levels, c_i, c_h, c_o, rank, act_fn, r_p, loss_type, us
     if network == "newfluidnet":
         return NewFluidNet(levels, c_i, c_h, c_o, dev, act_fn, r_p, loss_type, use_symm=use_symm, dilation=dilation,
                            a_bound=a_bound, repeats=repeats, use_skip=use_skip, f=kernel, p_pred=p_pred,
-                           spectral_conv=spectral_conv, blurr=blurr, drop_rate=dropout)
+                           spectral_conv=spectral_conv, blurr=blurr, drop_rate=dropout, factor=factor)
     if network in ("fluidnet", "ifluidnet"):            # (the reference builds the same FluidNet for both, :492)
         return FluidNet(levels, c_i, c_h, c_o, dev, act_fn, r_p, loss_type, use_symm=use_symm, dilation=dilation,
                         a_bound=a_bound, repeats=repeats, use_skip=use_skip, f=kernel, p_pred=p_pred,
@@ -571,7 +638,7 @@ def main(rank: int, world_size: int, save_every: int, total_epochs: int, batch_s
          sims_vec_init, times_vec_init, use_skip=False, p_pred=False, spectral_conv=False, dilation=1, a_bound=10,
          restart=False, advect=False, network="fluidnet", debug=False, scale=True, blurr=False, master_port=366,
          l2_reg=0.0, dropout=0.0, loss_scale=False, loss_derivative=False, roll_forward=1, factor=2, multi_scales=[],
-         synthetic=None, precision=None, lambda_mom=0.0, use_graph=False):
+         synthetic=None, precision=None, lambda_mom=0.0, use_graph=False, clip_norm=0.0, skip_nonfinite=False):
     ddp_setup(rank, world_size, master_port)
     dataset, dataset_init, model_uvp, model_AD, optimizer, scheduler, epoch = load_train_objs(
         rank, world_size, nn_dir, data_dir, levels, c_i, c_h, c_o, act_fn, r_p, loss_type, use_symm, repeats, kernel,
@@ -583,7 +650,8 @@ def main(rank: int, world_size: int, save_every: int, total_epochs: int, batch_s
     cv_data = prepare_dataloader(dataset["cv"], batch_size, world_size, rank)
     trainer = Trainer(model_uvp, model_AD, train_data, cv_data, None, None, optimizer, scheduler, rank, save_every,
                       nn_dir, p_pred, debug, network, loss_scale, loss_derivative, roll_forward, epoch=epoch,
-                      loss_type=loss_type, precision=precision, lambda_mom=lambda_mom, use_graph=use_graph)
+                      loss_type=loss_type, precision=precision, lambda_mom=lambda_mom, use_graph=use_graph,
+                      max_grad_norm=clip_norm, skip_nonfinite=skip_nonfinite)
     trainer.train(total_epochs)
     if dist.is_initialized():
         dist.destroy_process_group()
@@ -631,6 +699,8 @@ def build_arg_parser():
     p.add_argument("--lambda_mom", type=float, default=0.0)
     p.add_argument("--use_graph", type=int, default=0)
     p.add_argument("--epochs", type=int, default=None)
+    p.add_argument("--clip_norm", type=float, default=0.0)        # global gradient-norm clip (0 = off)
+    p.add_argument("--skip_nonfinite", type=int, default=0)       # 1: skip the optimizer step of a non-finite gradient
     return p
 
 
@@ -703,7 +773,7 @@ def cli(argv=None):
             a.use_skip == 1, p_pred, a.spectral_conv == 1, a.dilation, a.a_bound, a.restart == 1, a.advect == 1,
             a.network, debug, a.scale == 1, a.blurr == 1, a.master_port, a.l2_reg, a.drop_rate, a.loss_scale == 1,
             a.loss_derivative == 1, a.roll_forward, a.factor, a.multi_scales, synthetic, a.precision, a.lambda_mom,
-            a.use_graph == 1)
+            a.use_graph == 1, a.clip_norm, a.skip_nonfinite == 1)
     if world_size == 1:
         main(0, *args)
     else:
