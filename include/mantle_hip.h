@@ -506,10 +506,39 @@ int mc_assemble_adtime_batch(const float* T, const float* uv, const float* t, co
 /* The FluidNet family's dataset (NewADDataset.__getitem__, datasetio.py:595-654), same residency: T [m][h][w], uvp
  * [m][cy][h][w] (cy = 2 or 3: u, v[, p]), t [m] (the item's time weight).  For every item idx[b] writes
  *   x [b][7][h][w] = (xc/4, yc/4, log10(clip(eta,1e-8,1))/8, paras_nd x3, T),  y [b][cy][h][w] = (u/s, v/s[, p]),
- *   t_weight [b] = t[idx], scaler [b] = s.  (The reference's optional 1e-5 input noise is host-side and not reproduced.) */
+ *   t_weight [b] = t[idx], scaler [b] = s.  (No input noise here: mc_assemble_newad_step applies the reference's.) */
 int mc_assemble_newad_batch(const float* T, const float* uvp, const float* t, const float* paras, const float* paras_nd,
                             const float* xc, const float* yc, const int32_t* idx, int32_t b, int32_t m, int32_t cy,
                             int32_t h, int32_t w, float* x, float* y, float* t_weight, float* scaler, void* stream);
+
+/* ---- resident epoch loop: the batch is assembled inside the (captured) step ------------------------------------
+ * One item store = the resident arrays of one dataset, as the batch entry points above take them (uv [m][cy][h][w]). */
+typedef struct {
+  const float *T, *uv, *t, *paras, *paras_nd, *xc, *yc;
+  int32_t m;
+} mc_item_store;
+/* The item arithmetic of mc_assemble_*_batch (the same device functions: equal bits for equal items) with the indices read on
+ * the device: table int32 [rows][b] (ADTime: [rows][b][2]) is one epoch's batches, cursor uint32[4] = (step, steps, draw, 0)
+ * chooses row `step`; both pointers and the outputs are fixed, so one captured launch serves every replay.  An entry e >= 0
+ * is item e of main_store, e < 0 item -e - 1 of init_store (ADTime: the sign of a pair's first entry decides for both);
+ * init_store may be NULL when the table has no negative entry.  A cursor outside the table or an entry outside its store
+ * writes nothing for that row / batch slot (the host validates tables before upload).
+ * noise != 0 (NewAD; reference datasetio.py:604-613, which draws U(-1e-5, 1e-5) whatever the value): on the interior
+ * [2:h-2, 2:w-2]  T <- clip(T + n, 0, 1.35), the two-pixel frame keeps T, the viscosity channel follows the noisy T, the
+ * targets are unchanged.  n = (2u - 1) 1e-5, u = ((bits >> 8) + 0.5) 2^-24, bits = word 0 of Philox4x32-10 with key (seed_lo,
+ * seed_hi) and counter (pixel y * w + x, item | 0x80000000 for the init store, cursor draw, 0x6e6f6973): a pure function of
+ * (seed, draw, item, pixel), independent of launch shape and batch position. */
+int mc_assemble_adtime_step(const mc_item_store* main_store, const mc_item_store* init_store, const int32_t* table,
+                            const uint32_t* cursor, int32_t rows, int32_t b, int32_t cy, int32_t h, int32_t w, float* x, float* y,
+                            float* scaler, float* paras_out, void* stream);
+int mc_assemble_newad_step(const mc_item_store* main_store, const mc_item_store* init_store, const int32_t* table,
+                           const uint32_t* cursor, int32_t rows, int32_t b, int32_t cy, int32_t h, int32_t w, int32_t noise,
+                           uint32_t seed_lo, uint32_t seed_hi, float* x, float* y, float* t_weight, float* scaler, void* stream);
+/* One-thread kernel on `stream`: step = (step + 1) % steps, draw += 1.  Launched after the assembly, so every replay of a
+ * captured step consumes one table row and one noise draw. */
+int mc_loader_advance(uint32_t* cursor, void* stream);
+/* Host twin of the noise the kernel inlines (no device needed); item carries the store bit. */
+float mc_newad_noise_host(uint32_t seed_lo, uint32_t seed_hi, uint32_t draw, uint32_t item, uint32_t pixel);
 
 /* ---- Trainer.get_loss with roll_forward = R > 1 (multigpu.py:207-248): the network is applied R * R times in a chain, each
  * input rebuilt from channels 0..5 of the batch and the previous evaluation's T, u, v.  x [n][c][h][w] f32 (c >= 10) holds the

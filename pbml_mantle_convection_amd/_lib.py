@@ -64,6 +64,11 @@ def dropout_keep16(p: float) -> int:
     return min(max(int(round((1.0 - p) * 65536.0)), 1), 65535)
 
 
+class ItemStore(C.Structure):
+    """mc_item_store: the resident arrays of one dataset (T, uv, t, paras, paras_nd, xc, yc device pointers and the item count)."""
+    _fields_ = [(n, C.c_void_p) for n in ("T", "uv", "t", "paras", "paras_nd", "xc", "yc")] + [("m", C.c_int32)]
+
+
 class GradGuard(C.Structure):
     """mc_grad_guard: the device record of the guarded optimizer step (32 bytes)."""
     _fields_ = [("norm", C.c_float), ("coef", C.c_float), ("nonfinite", C.c_uint32), ("skip", C.c_uint32),
@@ -91,6 +96,7 @@ _CD, _GS, _LD = C.POINTER(ConvDesc), C.POINTER(GradSrc), C.POINTER(LossDesc)
 _CP, _CE = C.POINTER(ConvPrologue), C.POINTER(ConvEpilogue)
 _LN = C.POINTER(LearnedDesc)
 _DR, _u32, _u64 = C.POINTER(Dropout), C.c_uint32, C.c_uint64
+_IS = C.POINTER(ItemStore)
 
 # name -> (restype, argtypes); must list EVERY symbol include/mantle_hip.h declares
 SIGNATURES = {
@@ -178,6 +184,10 @@ SIGNATURES = {
     "mc_assemble_adtime_batch": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp,
                                            _vp, _vp, _vp]),
     "mc_assemble_newad_batch": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "mc_assemble_adtime_step": (C.c_int, [_IS, _IS, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "mc_assemble_newad_step": (C.c_int, [_IS, _IS, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _u32, _u32, _vp, _vp, _vp, _vp, _vp]),
+    "mc_loader_advance": (C.c_int, [_vp, _vp]),
+    "mc_newad_noise_host": (C.c_float, [_u32, _u32, _u32, _u32, _u32]),
     "mc_ts_build_input": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp]),
     "mc_ts_build_input_unet": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp]),
     "mc_roll_forward_update": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _vp]),
@@ -208,7 +218,7 @@ SIGNATURES = {
 VALUE_RETURNING = {"mc_version", "mc_strerror", "mc_conv_kernel_name", "mc_packed_weight_bytes", "mc_conv_bank_read_extent", "mc_conv_tiles",
                    "mc_wgrad_partial_bytes", "mc_gn_bwd_blocks",
                    "mc_learned_validate", "mc_learned_bank_bytes", "mc_learned_wgrad_workspace_bytes", "mc_fold_blocks", "mc_loss_fused_blocks",
-                   "mc_spectral_slots", "mc_philox4x32", "mc_grad_norm_blocks"}
+                   "mc_spectral_slots", "mc_philox4x32", "mc_grad_norm_blocks", "mc_newad_noise_host"}
 
 _lib = None
 

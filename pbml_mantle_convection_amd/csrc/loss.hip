@@ -4,6 +4,7 @@
 #include <cstdlib>
 #include <type_traits>
 #include "common.h"
+#include "philox.h"
 
 namespace {
 
@@ -603,47 +604,100 @@ __global__ __launch_bounds__(256) void k_loss_fused(LossGeom g, FusedIn in, cons
   bs.flush<15>(sums, slots);
 }
 
-// on-device batch assembly (ADTimeDataset.__getitem__, datasetio.py:229-280)
-__global__ void k_assemble_adtime(const float* __restrict__ T, const float* __restrict__ uv, const float* __restrict__ t,
-                                  const float* __restrict__ paras, const float* __restrict__ paras_nd,
-                                  const float* __restrict__ xc, const float* __restrict__ yc, const int* __restrict__ pairs,
-                                  int cy, int HW, float* __restrict__ x, float* __restrict__ y, float* __restrict__ scaler,
-                                  float* __restrict__ paras_out) {
-  const int b = blockIdx.y, i0 = pairs[2 * b], i1 = pairs[2 * b + 1];
-  const float raq = paras[i0 * 3], fkt = paras[i0 * 3 + 1], fkp = paras[i0 * 3 + 2];
-  const float lnfkt = logf(fkt), lnfkp = logf(fkp);
-  const float s = 5.0f * expf(raq * 0.1f * 1.80167667f + lnfkt * 0.4330392f + lnfkp * -0.46052953f);
-  const float inv_s = 1.0f / s, dt = t[i1] - t[i0];
-  const float n0 = paras_nd[i0 * 3], n1 = paras_nd[i0 * 3 + 1], n2 = paras_nd[i0 * 3 + 2];
+// ---- on-device batch assembly -------------------------------------------------------------------
+// One item store = the resident arrays of one dataset.  The per-item scalars and the per-pixel arithmetic are shared by the
+// batch kernels (indices from the caller) and the step kernels (indices from a device epoch table row chosen by a device
+// cursor), so that both give the same bits for the same items.
+struct ItemStore { const float *T, *uv, *t, *paras, *paras_nd, *xc, *yc; int m; };
+static ItemStore item_store(const mc_item_store* s) {
+  ItemStore r{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0};
+  if (s) r = ItemStore{s->T, s->uv, s->t, s->paras, s->paras_nd, s->xc, s->yc, s->m};
+  return r;
+}
+static bool item_store_ok(const mc_item_store* s) {
+  return s && s->T && s->uv && s->t && s->paras && s->paras_nd && s->xc && s->yc && s->m > 0;
+}
+struct ItemScalars { float raq, fkt, fkp, lnfkt, lnfkp, s, inv_s, n0, n1, n2; };
+__device__ __forceinline__ ItemScalars item_scalars(const float* __restrict__ paras, const float* __restrict__ paras_nd, int i0) {
+  ItemScalars q;
+  q.raq = paras[i0 * 3]; q.fkt = paras[i0 * 3 + 1]; q.fkp = paras[i0 * 3 + 2];
+  q.lnfkt = logf(q.fkt); q.lnfkp = logf(q.fkp);
+  q.s = 5.0f * expf(q.raq * 0.1f * 1.80167667f + q.lnfkt * 0.4330392f + q.lnfkp * -0.46052953f);
+  q.inv_s = 1.0f / q.s;
+  q.n0 = paras_nd[i0 * 3]; q.n1 = paras_nd[i0 * 3 + 1]; q.n2 = paras_nd[i0 * 3 + 2];
+  return q;
+}
+__device__ __forceinline__ float visc_channel(const ItemScalars& q, float Tp, float ycv) {
+  const float eta = expf(-q.lnfkt * Tp + q.lnfkp * (1.0f - ycv));
+  return log10f(fminf(fmaxf(eta, 1e-8f), 1.0f)) * 0.125f;
+}
+// the row of the epoch table the cursor points at: cursor = (step, steps, draw, 0); nullptr when the cursor lies outside the
+// table's `rows` (nothing is read or written then)
+__device__ __forceinline__ const int* table_row(const int* __restrict__ table, const uint32_t* __restrict__ cursor, int rows,
+                                                int row_words) {
+  const uint32_t step = cursor[0];
+  return step < (uint32_t)rows ? table + (size_t)step * row_words : nullptr;
+}
+
+// ADTimeDataset.__getitem__ (datasetio.py:229-280): item pair (i0, i1) of store S into batch slot b
+__device__ __forceinline__ void assemble_adtime_item(const ItemStore& S, int i0, int i1, int b, int cy, int HW, float* __restrict__ x,
+                                                     float* __restrict__ y, float* __restrict__ scaler,
+                                                     float* __restrict__ paras_out) {
+  const ItemScalars q = item_scalars(S.paras, S.paras_nd, i0);
+  const float dt = S.t[i1] - S.t[i0];
   if (blockIdx.x == 0 && threadIdx.x == 0) {
-    scaler[b] = s;
-    paras_out[b * 3] = raq; paras_out[b * 3 + 1] = fkt; paras_out[b * 3 + 2] = fkp;
+    scaler[b] = q.s;
+    paras_out[b * 3] = q.raq; paras_out[b * 3 + 1] = q.fkt; paras_out[b * 3 + 2] = q.fkp;
   }
-  const float* T0 = T + (size_t)i0 * HW;
-  const float* T1 = T + (size_t)i1 * HW;
-  const float* u0 = uv + ((size_t)i0 * cy + 0) * HW;
-  const float* v0 = uv + ((size_t)i0 * cy + 1) * HW;
-  const float* u1 = uv + ((size_t)i1 * cy + 0) * HW;
-  const float* v1 = uv + ((size_t)i1 * cy + 1) * HW;
+  const float* T0 = S.T + (size_t)i0 * HW;
+  const float* T1 = S.T + (size_t)i1 * HW;
+  const float* u0 = S.uv + ((size_t)i0 * cy + 0) * HW;
+  const float* v0 = S.uv + ((size_t)i0 * cy + 1) * HW;
+  const float* u1 = S.uv + ((size_t)i1 * cy + 0) * HW;
+  const float* v1 = S.uv + ((size_t)i1 * cy + 1) * HW;
   float* xb = x + (size_t)b * 10 * HW;
   float* yb = y + (size_t)b * 3 * HW;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < HW; i += gridDim.x * blockDim.x) {
-    const float Tp = T0[i], ycv = yc[i];
-    const float eta = expf(-lnfkt * Tp + lnfkp * (1.0f - ycv));
-    xb[i] = xc[i];
+    const float Tp = T0[i], ycv = S.yc[i];
+    xb[i] = S.xc[i];
     xb[HW + i] = ycv;
     xb[2 * (size_t)HW + i] = dt;
-    xb[3 * (size_t)HW + i] = n0;
-    xb[4 * (size_t)HW + i] = n1;
-    xb[5 * (size_t)HW + i] = n2;
-    xb[6 * (size_t)HW + i] = log10f(fminf(fmaxf(eta, 1e-8f), 1.0f)) * 0.125f;
+    xb[3 * (size_t)HW + i] = q.n0;
+    xb[4 * (size_t)HW + i] = q.n1;
+    xb[5 * (size_t)HW + i] = q.n2;
+    xb[6 * (size_t)HW + i] = visc_channel(q, Tp, ycv);
     xb[7 * (size_t)HW + i] = Tp;
-    xb[8 * (size_t)HW + i] = u0[i] * inv_s;
-    xb[9 * (size_t)HW + i] = v0[i] * inv_s;
-    yb[i] = u1[i] * inv_s;
-    yb[HW + i] = v1[i] * inv_s;
+    xb[8 * (size_t)HW + i] = u0[i] * q.inv_s;
+    xb[9 * (size_t)HW + i] = v0[i] * q.inv_s;
+    yb[i] = u1[i] * q.inv_s;
+    yb[HW + i] = v1[i] * q.inv_s;
     yb[2 * (size_t)HW + i] = T1[i];
   }
+}
+__global__ void k_assemble_adtime(ItemStore S, const int* __restrict__ pairs, int cy, int HW, float* __restrict__ x,
+                                  float* __restrict__ y, float* __restrict__ scaler, float* __restrict__ paras_out) {
+  const int b = blockIdx.y;
+  assemble_adtime_item(S, pairs[2 * b], pairs[2 * b + 1], b, cy, HW, x, y, scaler, paras_out);
+}
+// table [rows][B][2]: a pair with a negative first entry (e0, e1) is the pair (-e0 - 1, -e1 - 1) of the init store
+__global__ void k_assemble_adtime_step(ItemStore S0, ItemStore S1, const int* __restrict__ table, const uint32_t* __restrict__ cursor,
+                                       int rows, int cy, int HW, float* __restrict__ x, float* __restrict__ y,
+                                       float* __restrict__ scaler, float* __restrict__ paras_out) {
+  const int b = blockIdx.y;
+  const int* row = table_row(table, cursor, rows, 2 * gridDim.y);
+  if (!row) return;
+  int e0 = row[2 * b], e1 = row[2 * b + 1];
+  const bool init = e0 < 0;
+  if (init) { e0 = -(e0 + 1); e1 = -(e1 + 1); }
+  const ItemStore& S = init ? S1 : S0;
+  if ((uint32_t)e0 >= (uint32_t)S.m || (uint32_t)e1 >= (uint32_t)S.m) return;      // (a null init store has m = 0)
+  assemble_adtime_item(S, e0, e1, b, cy, HW, x, y, scaler, paras_out);
+}
+// cursor = (step, steps, draw, 0): the next replay reads the next row and draws other noise
+__global__ void k_loader_advance(uint32_t* __restrict__ cursor) {
+  const uint32_t steps = cursor[1];
+  cursor[0] = steps ? (cursor[0] + 1u) % steps : 0u;
+  cursor[2] += 1u;
 }
 
 // TS 'unet' branch (pytorch_networks_convae.py:411-446): 10-channel input and the wall / side conditions of the predicted T
@@ -703,37 +757,60 @@ __global__ void k_ts_wall_bc(const float* __restrict__ src, int H, int W, float*
   }
 }
 
-// on-device batch assembly for the FluidNet family (NewADDataset.__getitem__, datasetio.py:595-654)
-__global__ void k_assemble_newad(const float* __restrict__ T, const float* __restrict__ uvp, const float* __restrict__ t,
-                                 const float* __restrict__ paras, const float* __restrict__ paras_nd,
-                                 const float* __restrict__ xc, const float* __restrict__ yc, const int* __restrict__ idx,
-                                 int cy, int HW, float* __restrict__ x, float* __restrict__ y, float* __restrict__ tw,
-                                 float* __restrict__ scaler) {
-  const int b = blockIdx.y, i0 = idx[b];
-  const float raq = paras[i0 * 3], fkt = paras[i0 * 3 + 1], fkp = paras[i0 * 3 + 2];
-  const float lnfkt = logf(fkt), lnfkp = logf(fkp);
-  const float s = 5.0f * expf(raq * 0.1f * 1.80167667f + lnfkt * 0.4330392f + lnfkp * -0.46052953f);
-  const float inv_s = 1.0f / s;
-  const float n0 = paras_nd[i0 * 3], n1 = paras_nd[i0 * 3 + 1], n2 = paras_nd[i0 * 3 + 2];
-  if (blockIdx.x == 0 && threadIdx.x == 0) { scaler[b] = s; tw[b] = t[i0]; }
-  const float* T0 = T + (size_t)i0 * HW;
-  const float* yi = uvp + (size_t)i0 * cy * HW;
+// on-device batch assembly for the FluidNet family (NewADDataset.__getitem__, datasetio.py:595-654): item i0 of store S into
+// batch slot b.  NOISE (reference :604-613): T + n clipped to [0, 1.35] on the interior [2:H-2, 2:W-2], n = mc_newad_noise of
+// (seed, draw, item word, pixel); the two-pixel frame keeps the stored T; the viscosity channel follows the noisy T.
+template <bool NOISE>
+__device__ __forceinline__ void assemble_newad_item(const ItemStore& S, int i0, int b, int cy, int HW, int W, uint32_t seed_lo,
+                                                    uint32_t seed_hi, uint32_t draw, uint32_t item_word, float* __restrict__ x,
+                                                    float* __restrict__ y, float* __restrict__ tw, float* __restrict__ scaler) {
+  const ItemScalars q = item_scalars(S.paras, S.paras_nd, i0);
+  if (blockIdx.x == 0 && threadIdx.x == 0) { scaler[b] = q.s; tw[b] = S.t[i0]; }
+  const float* T0 = S.T + (size_t)i0 * HW;
+  const float* yi = S.uv + (size_t)i0 * cy * HW;
   float* xb = x + (size_t)b * 7 * HW;
   float* yb = y + (size_t)b * cy * HW;
+  const int H = HW / W;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < HW; i += gridDim.x * blockDim.x) {
-    const float Tp = T0[i], ycv = yc[i];
-    const float eta = expf(-lnfkt * Tp + lnfkp * (1.0f - ycv));
-    xb[i] = xc[i] * 0.25f;
+    float Tp = T0[i];
+    const float ycv = S.yc[i];
+    if (NOISE) {
+      const int r = i / W, c = i - r * W;
+      if (r >= 2 && r < H - 2 && c >= 2 && c < W - 2)
+        Tp = fminf(fmaxf(Tp + mc_newad_noise(seed_lo, seed_hi, draw, item_word, (uint32_t)i), 0.0f), 1.35f);
+    }
+    xb[i] = S.xc[i] * 0.25f;
     xb[HW + i] = ycv * 0.25f;
-    xb[2 * (size_t)HW + i] = log10f(fminf(fmaxf(eta, 1e-8f), 1.0f)) * 0.125f;
-    xb[3 * (size_t)HW + i] = n0;
-    xb[4 * (size_t)HW + i] = n1;
-    xb[5 * (size_t)HW + i] = n2;
+    xb[2 * (size_t)HW + i] = visc_channel(q, Tp, ycv);
+    xb[3 * (size_t)HW + i] = q.n0;
+    xb[4 * (size_t)HW + i] = q.n1;
+    xb[5 * (size_t)HW + i] = q.n2;
     xb[6 * (size_t)HW + i] = Tp;
-    yb[i] = yi[i] * inv_s;
-    yb[HW + i] = yi[HW + i] * inv_s;
+    yb[i] = yi[i] * q.inv_s;
+    yb[HW + i] = yi[HW + i] * q.inv_s;
     if (cy > 2) yb[2 * (size_t)HW + i] = yi[2 * (size_t)HW + i];
   }
+}
+__global__ void k_assemble_newad(ItemStore S, const int* __restrict__ idx, int cy, int HW, int W, float* __restrict__ x,
+                                 float* __restrict__ y, float* __restrict__ tw, float* __restrict__ scaler) {
+  const int b = blockIdx.y;
+  assemble_newad_item<false>(S, idx[b], b, cy, HW, W, 0u, 0u, 0u, 0u, x, y, tw, scaler);
+}
+// table [rows][B]: entry e >= 0 is item e of the main store, e < 0 item -e - 1 of the init store
+template <bool NOISE>
+__global__ void k_assemble_newad_step(ItemStore S0, ItemStore S1, const int* __restrict__ table, const uint32_t* __restrict__ cursor,
+                                      int rows, int cy, int HW, int W, uint32_t seed_lo, uint32_t seed_hi, float* __restrict__ x,
+                                      float* __restrict__ y, float* __restrict__ tw, float* __restrict__ scaler) {
+  const int b = blockIdx.y;
+  const int* row = table_row(table, cursor, rows, gridDim.y);
+  if (!row) return;
+  const int e = row[b];
+  const bool init = e < 0;
+  const int i0 = init ? -(e + 1) : e;
+  const ItemStore& S = init ? S1 : S0;
+  if ((uint32_t)i0 >= (uint32_t)S.m) return;                                       // (a null init store has m = 0)
+  assemble_newad_item<NOISE>(S, i0, b, cy, HW, W, seed_lo, seed_hi, cursor[2], (uint32_t)i0 | (init ? MC_NOISE_INIT_BIT : 0u), x, y,
+                             tw, scaler);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -977,14 +1054,16 @@ int mc_momentum_adjoint(const mc_loss_desc* d, const float* T, int64_t pbs, int6
   return MC_OK;
 }
 
+static dim3 assemble_grid(int32_t b, int32_t h, int32_t w) { return dim3(max(1, min(cdiv(h * w, 256 * 4), 256)), b); }
+
 int mc_assemble_adtime_batch(const float* T, const float* uv, const float* t, const float* paras, const float* paras_nd,
                              const float* xc, const float* yc, const int32_t* pairs, int32_t b, int32_t m, int32_t cy,
                              int32_t h, int32_t w, float* x, float* y, float* scaler, float* paras_out, void* stream) {
   if (!T || !uv || !t || !paras || !paras_nd || !xc || !yc || !pairs || !x || !y || !scaler || !paras_out) return MC_EINVAL;
   if (b <= 0 || m <= 0 || cy < 2 || h <= 0 || w <= 0) return MC_EINVAL;
-  dim3 grid(max(1, min(cdiv(h * w, 256 * 4), 256)), b);
-  hipLaunchKernelGGL(k_assemble_adtime, grid, dim3(256), 0, (hipStream_t)stream, T, uv, t, paras, paras_nd, xc, yc, pairs, cy,
-                     h * w, x, y, scaler, paras_out);
+  const ItemStore S{T, uv, t, paras, paras_nd, xc, yc, m};
+  hipLaunchKernelGGL(k_assemble_adtime, assemble_grid(b, h, w), dim3(256), 0, (hipStream_t)stream, S, pairs, cy, h * w, x, y, scaler,
+                     paras_out);
   MC_CHECK_LAUNCH();
   return MC_OK;
 }
@@ -994,11 +1073,51 @@ int mc_assemble_newad_batch(const float* T, const float* uvp, const float* t, co
                             int32_t w, float* x, float* y, float* t_weight, float* scaler, void* stream) {
   if (!T || !uvp || !t || !paras || !paras_nd || !xc || !yc || !idx || !x || !y || !t_weight || !scaler) return MC_EINVAL;
   if (b <= 0 || m <= 0 || cy < 2 || cy > 3 || h <= 0 || w <= 0) return MC_EINVAL;
-  dim3 grid(max(1, min(cdiv(h * w, 256 * 4), 256)), b);
-  hipLaunchKernelGGL(k_assemble_newad, grid, dim3(256), 0, (hipStream_t)stream, T, uvp, t, paras, paras_nd, xc, yc, idx, cy, h * w,
-                     x, y, t_weight, scaler);
+  const ItemStore S{T, uvp, t, paras, paras_nd, xc, yc, m};
+  hipLaunchKernelGGL(k_assemble_newad, assemble_grid(b, h, w), dim3(256), 0, (hipStream_t)stream, S, idx, cy, h * w, w, x, y,
+                     t_weight, scaler);
   MC_CHECK_LAUNCH();
   return MC_OK;
+}
+
+int mc_assemble_adtime_step(const mc_item_store* main_store, const mc_item_store* init_store, const int32_t* table,
+                            const uint32_t* cursor, int32_t rows, int32_t b, int32_t cy, int32_t h, int32_t w, float* x, float* y,
+                            float* scaler, float* paras_out, void* stream) {
+  if (!item_store_ok(main_store) || (init_store && !item_store_ok(init_store))) return MC_EINVAL;
+  if (!table || !cursor || !x || !y || !scaler || !paras_out) return MC_EINVAL;
+  if (rows <= 0 || b <= 0 || b > 65535 || cy < 2 || h <= 0 || w <= 0) return MC_EINVAL;
+  hipLaunchKernelGGL(k_assemble_adtime_step, assemble_grid(b, h, w), dim3(256), 0, (hipStream_t)stream, item_store(main_store),
+                     item_store(init_store), table, cursor, rows, cy, h * w, x, y, scaler, paras_out);
+  MC_CHECK_LAUNCH();
+  return MC_OK;
+}
+
+int mc_assemble_newad_step(const mc_item_store* main_store, const mc_item_store* init_store, const int32_t* table,
+                           const uint32_t* cursor, int32_t rows, int32_t b, int32_t cy, int32_t h, int32_t w, int32_t noise,
+                           uint32_t seed_lo, uint32_t seed_hi, float* x, float* y, float* t_weight, float* scaler, void* stream) {
+  if (!item_store_ok(main_store) || (init_store && !item_store_ok(init_store))) return MC_EINVAL;
+  if (!table || !cursor || !x || !y || !t_weight || !scaler) return MC_EINVAL;
+  if (rows <= 0 || b <= 0 || b > 65535 || cy < 2 || cy > 3 || h <= 0 || w <= 0) return MC_EINVAL;
+  const ItemStore S0 = item_store(main_store), S1 = item_store(init_store);
+  if (noise)
+    hipLaunchKernelGGL(k_assemble_newad_step<true>, assemble_grid(b, h, w), dim3(256), 0, (hipStream_t)stream, S0, S1, table, cursor,
+                       rows, cy, h * w, w, seed_lo, seed_hi, x, y, t_weight, scaler);
+  else
+    hipLaunchKernelGGL(k_assemble_newad_step<false>, assemble_grid(b, h, w), dim3(256), 0, (hipStream_t)stream, S0, S1, table, cursor,
+                       rows, cy, h * w, w, seed_lo, seed_hi, x, y, t_weight, scaler);
+  MC_CHECK_LAUNCH();
+  return MC_OK;
+}
+
+int mc_loader_advance(uint32_t* cursor, void* stream) {
+  if (!cursor) return MC_EINVAL;
+  hipLaunchKernelGGL(k_loader_advance, dim3(1), dim3(1), 0, (hipStream_t)stream, cursor);
+  MC_CHECK_LAUNCH();
+  return MC_OK;
+}
+
+float mc_newad_noise_host(uint32_t seed_lo, uint32_t seed_hi, uint32_t draw, uint32_t item, uint32_t pixel) {
+  return mc_newad_noise(seed_lo, seed_hi, draw, item, pixel);
 }
 
 int mc_ts_build_input(const float* T, const float* xc, const float* yc, const float* ycc, const float* paras,

@@ -1,4 +1,4 @@
-// Counter-based random bits for dropout: Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as
+// Counter-based random bits for dropout and the resident loader's input noise: Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as
 // 1, 2, 3", SC 2011).  Plain integer C++, the same text for the host and the device, so that the CPU tests pin exactly what
 // the GroupNorm / activation kernels inline.
 //
@@ -33,4 +33,18 @@ MC_HD uint32_t mc_dropout_keep8(uint32_t seed_lo, uint32_t seed_hi, uint32_t ste
 #pragma unroll
   for (int j = 0; j < 8; ++j) bits |= (((o[j >> 1] >> (16 * (j & 1))) & 0xffffu) < keep16 ? 1u : 0u) << j;
   return bits;
+}
+
+// Input noise of the resident NewAD loader (reference datasetio.py:604-613 draws U(-1e-5, 1e-5) per interior pixel): a pure
+// function of (seed, draw, item, pixel) -- key = (seed_lo, seed_hi), counter = (pixel, item, draw, MC_NOISE_TAG), item = the
+// item's index with bit 31 set for the initial-condition store.  With k = out[0] >> 8 and u = (k + 0.5) 2^-24,
+// n = (2u - 1) 1e-5 = ((2k + 1 - 2^24) 2^-24) 1e-5: the odd integer has fewer than 25 bits, so the f32 product is one
+// rounding of the exact value and |n| < 1e-5 strictly.
+#define MC_NOISE_TAG 0x6e6f6973u
+#define MC_NOISE_INIT_BIT 0x80000000u
+MC_HD float mc_newad_noise(uint32_t seed_lo, uint32_t seed_hi, uint32_t draw, uint32_t item, uint32_t pixel) {
+  uint32_t o[4];
+  mc_philox4x32_10(pixel, item, draw, MC_NOISE_TAG, seed_lo, seed_hi, o);
+  const int32_t odd = (int32_t)(2u * (o[0] >> 8) + 1u) - (1 << 24);
+  return ((float)odd * 5.9604644775390625e-8f) * 1e-5f;
 }

@@ -292,9 +292,14 @@ class ResidentADTimeDataset:
         self.indices, self.indices_init = list(ds.indices), list(ds.indices_init)
         self.M, self.cy, self.H, self.W = self.T.shape[0], self.uv.shape[1], self.T.shape[1], self.T.shape[2]
         self.device = dev
+        print(f"resident ADTimeDataset: {self.M} snapshots, {_resident_bytes(self)} bytes on {dev}")
 
     def __len__(self):
         return len(self.indices)
+
+    def store(self):
+        """The arrays as an `mc_item_store` (the tensors stay owned by this object)."""
+        return _item_store(self, self.uv)
 
     def pairs(self, idx):
         out = []
@@ -332,17 +337,17 @@ class ResidentNewADDataset:
     `mc_assemble_newad_batch` (the reference builds every item on the host in fp64: datasetio.py:595-654).  Stored once as
     f32: T [M,H,W], targets [M,cy,H,W] (u, v[, p]), time weights [M], parameters [M,3] (+ normalised), xc / yc [H,W].
     `assemble(idx)` returns device tensors (x [B,7,H,W], y [B,cy,H,W], t_weight [B], scaler [B]) — the 4-tuple of
-    `NewADDataset.__getitem__`, batched — and can write x, y straight into `Trainer.input_buffers()`.  The reference's
-    optional `noise` (a 1e-5 uniform perturbation of T drawn with numpy on the host) is not reproduced: the constructor
-    refuses a dataset built with noise > 0."""
+    `NewADDataset.__getitem__`, batched — and can write x, y straight into `Trainer.input_buffers()`.
 
-    def __init__(self, ds: "NewADDataset", device):
+    A dataset built with `noise > 0` switches the reference's input noise on (:604-613: U(-1e-5, 1e-5) on the interior of T
+    whatever the value, clipped to [0, 1.35]).  It is drawn on the device as a pure function of (`noise_seed`, draw, item,
+    pixel) (`mc_newad_noise_host` is the host twin); `assemble` takes the draw from an internal counter unless `draw` is given.
+    `is_init` marks the initial-condition store of a `ResidentLoader` (its items draw other noise than the main store's)."""
+
+    def __init__(self, ds: "NewADDataset", device, is_init=False, noise_seed=0):
         from . import _lib as L
         self._L = L
         L.load()
-        if getattr(ds, "noise", 0.0) > 0:
-            raise NotImplementedError("NewADDataset(noise > 0) draws host-side numpy noise per item; keep noise = 0 for the "
-                                      "resident form")
         if not ds.scale:
             raise NotImplementedError("scale=False returns nothing in the reference either")
         dev = torch.device(device)
@@ -357,19 +362,26 @@ class ResidentNewADDataset:
         self.yc = ds.yc.reshape(ds.yc.shape[-2], ds.yc.shape[-1]).to(**f).contiguous()
         self.M, self.cy, self.H, self.W = self.T.shape[0], self.uvp.shape[1], self.T.shape[1], self.T.shape[2]
         self.p_pred, self.device = ds.p_pred, dev
+        self.noise = getattr(ds, "noise", 0.0) > 0
+        self.is_init, self.noise_seed, self.draw = bool(is_init), int(noise_seed), 0
+        print(f"resident NewADDataset: {self.M} items, {_resident_bytes(self)} bytes on {dev}")
 
     def __len__(self):
         return self.M
 
-    def assemble(self, idx, out=None):
+    def store(self):
+        """The arrays as an `mc_item_store` (the tensors stay owned by this object)."""
+        return _item_store(self, self.uvp)
+
+    def assemble(self, idx, out=None, draw=None):
         """idx: iterable of item indices.  out: optional dict with preallocated 'gVTp' [B,7,H,W] and 'uvp' [B,cy,H,W] f32
-        device tensors (e.g. Trainer.input_buffers())."""
+        device tensors (e.g. Trainer.input_buffers()).  draw: the noise draw (default: the internal counter, which then
+        advances by one)."""
         L = self._L
         idx = [int(i) for i in idx]
         if not idx or min(idx) < 0 or max(idx) >= self.M:
             raise IndexError("item index out of range")
         B = len(idx)
-        itab = torch.tensor(idx, dtype=torch.int32).to(self.device, non_blocking=True)
         f = dict(dtype=torch.float32, device=self.device)
         o = out or {}
         x = o.get("gVTp") if o.get("gVTp") is not None else torch.empty((B, 7, self.H, self.W), **f)
@@ -377,10 +389,225 @@ class ResidentNewADDataset:
         if tuple(x.shape) != (B, 7, self.H, self.W) or tuple(y.shape) != (B, self.cy, self.H, self.W):
             raise ValueError("output buffers do not match the batch shape")
         tw, sc = torch.empty((B,), **f), torch.empty((B,), **f)
+        if self.noise:
+            # a one-row epoch table through the step kernel (the batch entry point has no noise arguments)
+            if draw is None:
+                draw, self.draw = self.draw, self.draw + 1
+            itab = torch.tensor([-(i + 1) for i in idx] if self.is_init else idx, dtype=torch.int32).to(self.device)
+            cursor = torch.from_numpy(np.array([0, 1, int(draw) & 0xFFFFFFFF, 0], dtype=np.uint32).view(np.int32)).to(self.device)
+            st = self.store()
+            import ctypes as C
+            L.call("mc_assemble_newad_step", C.byref(st), C.byref(st) if self.is_init else None, L.ptr(itab), L.ptr(cursor), 1, B,
+                   self.cy, self.H, self.W, 1, self.noise_seed & 0xFFFFFFFF, (self.noise_seed >> 32) & 0xFFFFFFFF, L.ptr(x),
+                   L.ptr(y), L.ptr(tw), L.ptr(sc), L.stream())
+            return x, y, tw, sc
+        itab = torch.tensor(idx, dtype=torch.int32).to(self.device, non_blocking=True)
         L.call("mc_assemble_newad_batch", L.ptr(self.T), L.ptr(self.uvp), L.ptr(self.t), L.ptr(self.paras), L.ptr(self.paras_nd),
                L.ptr(self.xc), L.ptr(self.yc), L.ptr(itab), B, self.M, self.cy, self.H, self.W, L.ptr(x), L.ptr(y), L.ptr(tw),
                L.ptr(sc), L.stream())
         return x, y, tw, sc
+
+
+def _resident_bytes(res):
+    return sum(t.numel() * t.element_size() for t in vars(res).values() if isinstance(t, torch.Tensor))
+
+
+def _item_store(res, uv):
+    L = res._L
+    return L.ItemStore(L.ptr(res.T), L.ptr(uv), L.ptr(res.t), L.ptr(res.paras), L.ptr(res.paras_nd), L.ptr(res.xc), L.ptr(res.yc),
+                       res.M)
+
+
+# --------------------------------------------------------------------------------------------------
+# resident epoch loop: one epoch's batches as a device table, assembled inside the (captured) step
+# --------------------------------------------------------------------------------------------------
+def loader_seed(seed: int, rank: int = 0) -> int:
+    """64-bit noise seed of a rank's loader: low word seed + rank (ranks draw different noise), high word a fixed tag."""
+    return (0x4C4F4144 << 32) | ((int(seed) + int(rank)) & 0xFFFFFFFF)
+
+
+def epoch_steps(shard_sizes, batch_size, small_batch=0):
+    """Steps per epoch: the minimum over the ranks' shards of items // (batch_size - small_batch) -- shards differ by up to
+    one item, and ranks that ran different step counts would hang the all-reduce."""
+    bm = int(batch_size) - int(small_batch)
+    if bm <= 0:
+        raise ValueError(f"batch_size {batch_size} leaves no room for main items beside small_batch {small_batch}")
+    return min(int(n) // bm for n in shard_sizes)
+
+
+def epoch_table(n_main, batch_size, small_batch=0, n_init=0, *, seed=0, epoch=0, rank=0, steps=None, pairs=None,
+                pairs_init=None):
+    """One epoch's batches as an int32 table [steps, B] (host, pure): drawn from a torch.Generator seeded with (seed, epoch,
+    rank).  Main items are the dataset in shuffled order in rows of B - small_batch, the last short row dropped
+    (prepare_dataloader's drop_last=True); every row gets small_batch items of the init set, distinct within the row (what the
+    reference's next(iter(loader_init)) yields, multigpu.py:353-357), stored as -(i + 1); then every row is permuted as a
+    whole (:358-360).  With `pairs` (ADTimeDataset.indices) the table is [steps, B, 2]: entry i becomes pairs[i], replaced by
+    a random pair of `pairs_init` when its first index is a multiple of 8 (datasetio.py:236-237) -- those draws come last, so
+    the index table of the same (seed, epoch, rank) is what the pairs were looked up from."""
+    B, sb = int(batch_size), int(small_batch)
+    bm = B - sb
+    if sb < 0 or bm <= 0:
+        raise ValueError(f"batch_size {B} / small_batch {sb}: need 0 <= small_batch < batch_size")
+    if sb > n_init:
+        raise ValueError(f"small_batch {sb} needs at least as many init items, the init set has {n_init}")
+    if pairs is not None and sb:
+        raise ValueError("the ADTime table takes its initial-condition pairs from the dataset itself: small_batch must be 0")
+    g = torch.Generator(device="cpu")
+    g.manual_seed(((int(seed) & 0xFFFFFFFF) << 31) ^ ((int(epoch) & 0xFFFFF) << 11) ^ (int(rank) & 0x7FF))
+    most = int(n_main) // bm
+    steps = most if steps is None else int(steps)
+    if steps > most:
+        raise ValueError(f"{steps} steps of {bm} main items need more than the {n_main} items of the dataset")
+    tab = torch.randperm(int(n_main), generator=g)[: steps * bm].view(steps, bm)
+    if sb and steps:
+        init = torch.stack([torch.randperm(int(n_init), generator=g)[:sb] for _ in range(steps)]).view(steps, sb)
+        tab = torch.cat((tab, -(init + 1)), dim=1)
+        order = torch.stack([torch.randperm(B, generator=g) for _ in range(steps)]).view(steps, B)
+        tab = torch.gather(tab, 1, order)
+    if pairs is None:
+        return tab.to(torch.int32).contiguous()
+    pr = torch.tensor(pairs, dtype=torch.int64).view(-1, 2)[tab]                 # [steps, B, 2]
+    if pairs_init is not None and len(pairs_init):
+        pi = torch.tensor(pairs_init, dtype=torch.int64).view(-1, 2)
+        pick = torch.randint(0, pi.shape[0], (steps, B), generator=g)
+        pr = torch.where((pr[..., :1] % 8 == 0), pi[pick], pr)
+    return pr.to(torch.int32).contiguous()
+
+
+def validate_table(tab, m_main, m_init=0):
+    """Every entry of an epoch table against the store sizes (host, before upload): e >= 0 needs e < m_main, e < 0 needs
+    -e - 1 < m_init; the two entries of a pair come from the same store."""
+    t = tab.to(torch.int64)
+    if t.numel() == 0:
+        return
+    if int(t.max()) >= int(m_main) or int(t.min()) < -int(m_init):
+        raise IndexError(f"epoch table entry outside its store: range [{int(t.min())}, {int(t.max())}] for {m_main} main and "
+                         f"{m_init} init items")
+    if t.dim() == 3 and bool(((t[..., 0] < 0) != (t[..., 1] < 0)).any()):
+        raise IndexError("epoch table pair with entries from two stores")
+
+
+class ResidentLoader:
+    """Iterable over one epoch's batches of a resident dataset (and, for the FluidNet family, a resident initial-condition set:
+    `small_batch` of its items go into every batch, reference multigpu.py:353-361, 866-884).  `start_epoch(epoch)` uploads the
+    epoch's table (`epoch_table`) into one fixed device buffer; `next_batch()` launches the assembly of the row the device
+    cursor points at and the cursor's advance on the current stream.  Table, cursor and output tensors never move, so a captured
+    step that contains `launch()` consumes one row per replay (Trainer, use_graph=True).  len() = steps per epoch, the
+    minimum over `shard_sizes` (the ranks' item counts; default: this rank's alone)."""
+
+    def __init__(self, resident, resident_init=None, batch_size=None, small_batch=0, seed=0, rank=0, world=1, shard_sizes=None):
+        from . import _lib as L
+        self._L = L
+        self.res, self.res_init = resident, resident_init
+        self.adtime = isinstance(resident, ResidentADTimeDataset)
+        if resident_init is None:
+            small_batch = 0
+        elif self.adtime:
+            raise ValueError("the ADTime dataset holds its own initial-condition pairs: resident_init must be None")
+        elif (resident_init.H, resident_init.W, resident_init.cy) != (resident.H, resident.W, resident.cy):
+            raise ValueError("the init set has another grid or target count than the main set")
+        if batch_size is None:
+            raise ValueError("batch_size is required")
+        self.B, self.small_batch, self.seed, self.rank, self.world = int(batch_size), int(small_batch), int(seed), int(rank), int(world)
+        self.n_main = len(resident)
+        self.n_init = len(resident_init) if self.small_batch else 0
+        self.steps = epoch_steps(shard_sizes if shard_sizes is not None else [self.n_main], self.B, self.small_batch)
+        if self.steps * (self.B - self.small_batch) > self.n_main:
+            raise ValueError("shard_sizes promise more items than the resident dataset holds")
+        dev = self.device = resident.device
+        self.noise = bool(getattr(resident, "noise", False))
+        self.seed64 = loader_seed(seed, rank)
+        if not self.adtime:
+            resident.noise_seed = self.seed64
+            if resident_init is not None:
+                resident_init.noise_seed, resident_init.is_init = self.seed64, True
+        self._store = resident.store()
+        self._store_init = resident_init.store() if self.small_batch else None
+        rows = max(self.steps, 1)
+        self.rows = rows
+        self.table = torch.zeros((rows, self.B, 2) if self.adtime else (rows, self.B), dtype=torch.int32, device=dev)
+        self.table_host = self.table.cpu()
+        self.cursor = torch.zeros(4, dtype=torch.int32, device=dev)
+        self.set_cursor(0, 0)
+        f = dict(dtype=torch.float32, device=dev)
+        H, W = resident.H, resident.W
+        if self.adtime:
+            self.out = dict(gVTp=torch.zeros((self.B, 10, H, W), **f), uvp=torch.zeros((self.B, 3, H, W), **f),
+                            scaler=torch.zeros((self.B,), **f), paras=torch.zeros((self.B, 3), **f))
+        else:
+            self.out = dict(gVTp=torch.zeros((self.B, 7, H, W), **f), uvp=torch.zeros((self.B, resident.cy, H, W), **f),
+                            scaler=torch.zeros((self.B,), **f), t_weight=torch.zeros((self.B,), **f))
+        self.epoch = None
+
+    def __len__(self):
+        return self.steps
+
+    def build_table(self, epoch):
+        if self.adtime:
+            return epoch_table(self.n_main, self.B, seed=self.seed, epoch=epoch, rank=self.rank, steps=self.steps,
+                               pairs=self.res.indices, pairs_init=self.res.indices_init)
+        return epoch_table(self.n_main, self.B, self.small_batch, self.n_init, seed=self.seed, epoch=epoch, rank=self.rank,
+                           steps=self.steps)
+
+    def set_cursor(self, step, draw):
+        """cursor = (step, steps, draw, 0) from the host (one small copy on the current stream)."""
+        host = np.array([int(step), self.steps, int(draw) & 0xFFFFFFFF, 0], dtype=np.uint32)
+        self.cursor.copy_(torch.from_numpy(host.view(np.int32)))
+
+    def cursor_state(self):
+        """(step, draw) of the device cursor (host sync; for set-up and tests, never per step)."""
+        c = self.cursor.cpu().numpy().view(np.uint32)
+        return int(c[0]), int(c[2])
+
+    def start_epoch(self, epoch, table=None):
+        """Uploads the epoch's table (one H2D copy into the fixed buffer) and rewinds the cursor's step; the draw goes on."""
+        tab = self.build_table(epoch) if table is None else table.to(torch.int32)
+        if tuple(tab.shape) != tuple(self.table.shape) and self.steps:
+            raise ValueError(f"epoch table of shape {tuple(tab.shape)}, the loader holds {tuple(self.table.shape)}")
+        validate_table(tab, self.res.M if self.adtime else self.n_main, self.n_init)
+        if self.steps:
+            self.table_host = tab
+            self.table.copy_(tab)
+        self.cursor[0:1].zero_()
+        self.epoch = epoch
+
+    def launch(self, out=None):
+        """The assembly of the cursor's row into `out` (default: the loader's own fixed tensors) and the cursor's advance, on
+        the current stream; capturable."""
+        import ctypes as C
+        L, o, r = self._L, (out or self.out), self.res
+        for k, v in self.out.items():
+            if k in o and o[k] is not None and tuple(o[k].shape) != tuple(v.shape):
+                raise ValueError(f"output buffer {k!r} of shape {tuple(o[k].shape)}, expected {tuple(v.shape)}")
+        g = lambda k: o[k] if o.get(k) is not None else self.out[k]  # noqa: E731
+        init = C.byref(self._store_init) if self._store_init is not None else None
+        if self.adtime:
+            L.call("mc_assemble_adtime_step", C.byref(self._store), init, L.ptr(self.table), L.ptr(self.cursor), self.rows, self.B,
+                   r.cy, r.H, r.W, L.ptr(g("gVTp")), L.ptr(g("uvp")), L.ptr(g("scaler")), L.ptr(g("paras")), L.stream())
+        else:
+            L.call("mc_assemble_newad_step", C.byref(self._store), init, L.ptr(self.table), L.ptr(self.cursor), self.rows, self.B,
+                   r.cy, r.H, r.W, int(self.noise), self.seed64 & 0xFFFFFFFF, self.seed64 >> 32, L.ptr(g("gVTp")),
+                   L.ptr(g("uvp")), L.ptr(g("t_weight")), L.ptr(g("scaler")), L.stream())
+        L.call("mc_loader_advance", L.ptr(self.cursor), L.stream())
+        return g
+
+    def batch(self, g=None):
+        """The output tensors in the item layout of the host datasets (what Trainer._unpack expects)."""
+        g = g or (lambda k: self.out[k])
+        r = self.res
+        if self.adtime:
+            return g("gVTp"), g("uvp"), g("scaler"), g("paras").view(self.B, 3, 1, 1), r.yc.view(1, r.H, r.W)
+        return g("gVTp"), g("uvp"), g("t_weight"), g("scaler")
+
+    def next_batch(self, out=None):
+        """Assembles the next batch on the device (no host copy): the eager form of the loop and the cv form."""
+        if self.epoch is None:
+            self.start_epoch(0)
+        return self.batch(self.launch(out))
+
+    def __iter__(self):
+        for _ in range(self.steps):
+            yield self.next_batch()
 
 
 def synthetic_batch(B, H, W, seed, *, p_pred=True, device="cpu", dtype=torch.float32, channels=None):

@@ -369,27 +369,40 @@ class Trainer:
         self._optim_step()
         return out8
 
-    def _graph_step(self, gVTp, uvp, yc, paras, scaler):
+    def _graph_step(self, gVTp, uvp, yc, paras, scaler, loader=None):
+        """`loader`: a ResidentLoader whose fixed output tensors ARE the step's inputs; its assembly launch and cursor advance
+        are captured at the head of the step graph, so a replay consumes the next row of the epoch table."""
         if self._graph is None:
-            st = dict(gVTp=gVTp.clone(), uvp=uvp.clone(),
-                      yc=None if yc is None else yc.clone().float(),
-                      paras=None if paras is None else paras.clone().float(),
-                      scaler=None if scaler is None else scaler.clone().float())
+            if loader is not None:                  # the loader's own tensors are the static buffers: nothing to copy, ever
+                st = dict(gVTp=gVTp, uvp=uvp, yc=yc, paras=paras, scaler=scaler)
+            else:
+                st = dict(gVTp=gVTp.clone(), uvp=uvp.clone(),
+                          yc=None if yc is None else yc.clone().float(),
+                          paras=None if paras is None else paras.clone().float(),
+                          scaler=None if scaler is None else scaler.clone().float())
             self._static = st
+            self._graph_loader = loader
             side = torch.cuda.Stream(device=self.device)
             side.wait_stream(torch.cuda.current_stream())
             eng = self.model_uvp.engine()
             drop_step = eng.dropout_step()          # (0 before the engine is planned)
+            cursor = loader.cursor_state() if loader is not None else None
             with torch.cuda.stream(side):           # warm-up: allocates every engine buffer outside the capture
+                if loader is not None:
+                    loader.launch()
                 self._fwd_bwd(st["gVTp"], st["uvp"], st["yc"], st["paras"], st["scaler"], train=True)
             torch.cuda.current_stream().wait_stream(side)
             torch.cuda.synchronize(self.device)
             eng.set_dropout_step(drop_step)         # the warm-up consumes no dropout step: eager and captured runs see 1, 2, 3, ...
+            if loader is not None:
+                loader.set_cursor(*cursor)          # ... nor a table row or a noise draw
             # with a process group alive its watchdog thread polls events while we capture: only calls of THIS thread may
             # invalidate the capture (the default "global" mode would turn the watchdog's event query into a capture error)
             mode = dict(capture_error_mode="thread_local") if (dist.is_available() and dist.is_initialized()) else {}
             self._graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self._graph, **mode):
+                if loader is not None:
+                    loader.launch()
                 self._static_out = self._fwd_bwd(st["gVTp"], st["uvp"], st["yc"], st["paras"], st["scaler"],
                                                  train=True)
             # Adam is a graph of its own: for world > 1 the flat-gradient all-reduce runs between the two replays
@@ -401,6 +414,8 @@ class Trainer:
             self.model_uvp.engine().freeze()
             self.loss.freeze()
         st = self._static
+        if loader is not self._graph_loader:
+            raise RuntimeError("the captured step assembles its batch from the loader it was captured with")
         # a captured step reads its inputs from fixed buffers; a caller that fills `input_buffers()` in place (a loader
         # writing the next batch straight into them) passes those very tensors and no copy is made
         if yc is not None and st["yc"] is not None and yc.data_ptr() != st["yc"].data_ptr():
@@ -458,7 +473,59 @@ class Trainer:
             return data[0], data[1], data[2], data[3], data[4]      # x, y, scaler, paras, yc (ADTimeDataset)
         return data[0], data[1], data[3] if len(data) > 3 else None, None, None
 
+    def resident_step(self, loader, is_train=True):
+        """One step on the next batch of a ResidentLoader: no host copy.  With use_graph the training step's replay assembles
+        the batch itself (the loader's launch is part of the captured graph); otherwise, and for evaluation, `next_batch()`
+        then the eager step on its device tensors.  The loader's one mesh is the dataset's: no per-batch mesh check."""
+        if is_train and self.use_graph:
+            gVTp, uvp, yc, paras, scaler = self._prep(*self._unpack(loader.batch()))
+            self._sync_lr()
+            return self._graph_step(gVTp, uvp, yc, paras, scaler, loader=loader)
+        gVTp, uvp, yc, paras, scaler = self._prep(*self._unpack(loader.next_batch()))
+        if is_train:
+            self._sync_lr()
+            out8 = self._fwd_bwd(gVTp, uvp, yc, paras, scaler, train=True)
+            allreduce_flat(self.flat.grad)
+            self._optim_step()
+            return out8
+        return self.eval_step(gVTp, uvp, yc, paras, scaler)
+
+    def _run_epoch_resident(self, epoch):
+        """_run_epoch on ResidentLoaders: per step the host issues the step's launches (graph replays with use_graph) and the
+        accumulation of its eight scalars; the log line every log_every steps is the only host sync."""
+        train, cv = self.train_data, self.cv_data
+        print(f"[GPU{self.gpu_id}] Epoch {epoch} | Batchsize: {train.B} | Steps: {len(train)}")
+        acc = torch.zeros(8, dtype=torch.float64, device=self.device)
+        cnt = torch.zeros((), dtype=torch.float64, device=self.device)
+        zero = torch.zeros(8, dtype=torch.float64, device=self.device)
+        train.start_epoch(epoch)
+        for i in range(len(train)):
+            t0 = time.time()
+            out8 = self.resident_step(train, True).double()
+            if self._guard is None:
+                acc += out8
+                cnt += 1.0
+            else:                                               # (as _run_train_guarded: skipped batches stay out of the means)
+                ok = torch.isfinite(out8).all()
+                acc += torch.where(ok, out8, zero)
+                cnt += ok
+            if i % self.log_every == 0:                         # the only host sync in the hot loop
+                print(epoch, (acc[:6] / cnt.clamp(min=1.0)).tolist(), time.time() - t0)
+                self.check_guard()
+        self.losses = (acc[:6] / cnt.clamp(min=1.0)).tolist()
+        if self._guard is not None:
+            self._skipped_seen = max(self._skipped_seen, self.check_guard()["skipped"])
+        acc.zero_()
+        with torch.no_grad():
+            print(f"[GPU{self.gpu_id}] Epoch CV {epoch} | Batchsize: {cv.B} | Steps: {len(cv)}")
+            cv.start_epoch(epoch)
+            for _ in range(len(cv)):
+                acc += self.resident_step(cv, False).double()
+        self.losses_cv = (acc[:6] / max(len(cv), 1)).tolist()
+
     def _run_epoch(self, epoch):
+        if isinstance(self.train_data, ResidentLoader):     # noqa: F405
+            return self._run_epoch_resident(epoch)
         print(f"[GPU{self.gpu_id}] Epoch {epoch} | Steps: {len(self.train_data)}")
         acc = torch.zeros(8, dtype=torch.float64, device=self.device)
         i = -1
@@ -633,21 +700,46 @@ def prepare_dataloader(dataset: Dataset, batch_size: int, world_size, rank):
                       drop_last=True)
 
 
+def resident_loader(ds, ds_init, batch_size: int, rank, world_size: int, n_items: int, seed: int = 0):
+    """The `--resident 1` form of prepare_dataloader: the host dataset (and, where there is one, its initial-condition set)
+    moved into HBM, and a ResidentLoader over it with the reference's small_batch (2, or 1 when world_size > 1, :866-868).
+    Steps per epoch come from every rank's shard of the n_items index entries, computed here without communication."""
+    dev = torch.device("cuda", rank) if isinstance(rank, int) else torch.device(rank)
+    r = rank if isinstance(rank, int) else 0
+    if isinstance(ds, ADTimeDataset):                                                  # noqa: F405
+        res, res_init = ResidentADTimeDataset(ds, dev), None                           # noqa: F405
+    else:
+        res = ResidentNewADDataset(ds, dev)                                            # noqa: F405
+        res_init = ResidentNewADDataset(ds_init, dev, is_init=True) if ds_init is not None else None   # noqa: F405
+    small_batch = 0 if res_init is None else (1 if world_size > 1 else 2)
+    spans = [shard_range(n_items, world_size, k) for k in range(world_size)]
+    return ResidentLoader(res, res_init, batch_size=batch_size, small_batch=small_batch, seed=seed, rank=r,   # noqa: F405
+                          world=world_size, shard_sizes=[hi - lo for lo, hi in spans] + [len(res)])
+
+
 def main(rank: int, world_size: int, save_every: int, total_epochs: int, batch_size: int, nn_dir, data_dir, levels,
          c_i, c_h, c_o, act_fn, r_p, loss_type, use_symm, repeats, kernel, milestones, sims_vec, times_vec,
          sims_vec_init, times_vec_init, use_skip=False, p_pred=False, spectral_conv=False, dilation=1, a_bound=10,
          restart=False, advect=False, network="fluidnet", debug=False, scale=True, blurr=False, master_port=366,
          l2_reg=0.0, dropout=0.0, loss_scale=False, loss_derivative=False, roll_forward=1, factor=2, multi_scales=[],
-         synthetic=None, precision=None, lambda_mom=0.0, use_graph=False, clip_norm=0.0, skip_nonfinite=False):
+         synthetic=None, precision=None, lambda_mom=0.0, use_graph=False, clip_norm=0.0, skip_nonfinite=False, noise=0.0,
+         resident=False):
+    if resident and synthetic is not None:
+        raise ValueError("--resident 1 keeps shard-file datasets in HBM; the --synthetic set has no shard files (leave "
+                         "--resident at 0 with --synthetic)")
     ddp_setup(rank, world_size, master_port)
     dataset, dataset_init, model_uvp, model_AD, optimizer, scheduler, epoch = load_train_objs(
         rank, world_size, nn_dir, data_dir, levels, c_i, c_h, c_o, act_fn, r_p, loss_type, use_symm, repeats, kernel,
         milestones, sims_vec, times_vec, sims_vec_init, times_vec_init, use_skip=use_skip, p_pred=p_pred,
         spectral_conv=spectral_conv, dilation=dilation, a_bound=a_bound, restart=restart, advect=advect,
-        network=network, scale=scale, debug=debug, blurr=blurr, l2_reg=l2_reg, dropout=dropout,
+        network=network, scale=scale, noise=noise, debug=debug, blurr=blurr, l2_reg=l2_reg, dropout=dropout,
         roll_forward=roll_forward, factor=factor, multi_scales=multi_scales, synthetic=synthetic)
-    train_data = prepare_dataloader(dataset["train"], batch_size, world_size, rank)
-    cv_data = prepare_dataloader(dataset["cv"], batch_size, world_size, rank)
+    if resident:
+        train_data, cv_data = (resident_loader(dataset[an], dataset_init[an], batch_size, rank, world_size,
+                                               len(sims_vec[an]), seed=torch.initial_seed()) for an in ("train", "cv"))
+    else:
+        train_data = prepare_dataloader(dataset["train"], batch_size, world_size, rank)
+        cv_data = prepare_dataloader(dataset["cv"], batch_size, world_size, rank)
     trainer = Trainer(model_uvp, model_AD, train_data, cv_data, None, None, optimizer, scheduler, rank, save_every,
                       nn_dir, p_pred, debug, network, loss_scale, loss_derivative, roll_forward, epoch=epoch,
                       loss_type=loss_type, precision=precision, lambda_mom=lambda_mom, use_graph=use_graph,
@@ -701,6 +793,7 @@ def build_arg_parser():
     p.add_argument("--epochs", type=int, default=None)
     p.add_argument("--clip_norm", type=float, default=0.0)        # global gradient-norm clip (0 = off)
     p.add_argument("--skip_nonfinite", type=int, default=0)       # 1: skip the optimizer step of a non-finite gradient
+    p.add_argument("--resident", type=int, default=0)             # 1: datasets resident in HBM, batches assembled inside the step
     return p
 
 
@@ -740,6 +833,9 @@ def channels_for(network, loss_type, p_pred):
 def cli(argv=None):
     import torch.multiprocessing as mp
     a = build_arg_parser().parse_args(argv)
+    if a.resident == 1 and a.synthetic is not None:
+        raise ValueError("--resident 1 keeps shard-file datasets in HBM; the --synthetic set has no shard files (leave "
+                         "--resident at 0 with --synthetic)")
     if a.gpu_nums:
         os.environ["HIP_VISIBLE_DEVICES"] = a.gpu_nums
     world_size = max(torch.cuda.device_count(), 1)
@@ -767,13 +863,16 @@ def cli(argv=None):
             init = get_indices_time if a.network == "unet" else get_indices   # noqa: F405
             sims_vec[an], times_vec[an] = init(a.data_dir, an, is_init=False, debug=debug,
                                                roll_forward=a.roll_forward)
-            sims_init[an], times_init[an] = None, None
+            if debug:
+                sims_init[an], times_init[an] = None, None
+            else:                                  # the initial-condition sets of a non-debug run (reference :1102-1107)
+                sims_init[an], times_init[an] = init(a.data_dir, an, is_init=True, debug=debug, roll_forward=a.roll_forward)
     args = (world_size, 1, epochs, a.batch_size, nn_dir, a.data_dir, a.levels, c_i, a.c_h, c_o, a.act_fn, a.r_p,
             a.loss_type, a.use_symm == 1, a.repeats, a.kernel, milestones, sims_vec, times_vec, sims_init, times_init,
             a.use_skip == 1, p_pred, a.spectral_conv == 1, a.dilation, a.a_bound, a.restart == 1, a.advect == 1,
             a.network, debug, a.scale == 1, a.blurr == 1, a.master_port, a.l2_reg, a.drop_rate, a.loss_scale == 1,
             a.loss_derivative == 1, a.roll_forward, a.factor, a.multi_scales, synthetic, a.precision, a.lambda_mom,
-            a.use_graph == 1, a.clip_norm, a.skip_nonfinite == 1)
+            a.use_graph == 1, a.clip_norm, a.skip_nonfinite == 1, a.noise, a.resident == 1)
     if world_size == 1:
         main(0, *args)
     else:
