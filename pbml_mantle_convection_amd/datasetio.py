@@ -559,6 +559,27 @@ class ResidentLoader:
         c = self.cursor.cpu().numpy().view(np.uint32)
         return int(c[0]), int(c[2])
 
+    def _push_noise_seed(self):
+        if not self.adtime:
+            self.res.noise_seed = self.seed64
+            if self.res_init is not None:
+                self.res_init.noise_seed = self.seed64
+
+    def state(self):
+        """What the next epoch's batches depend on beside the constructor's arguments (plain numbers; one host sync): the table
+        seed, the 64-bit noise seed, the datasets' noise_seed and the device cursor.  The epoch's table is a pure function of
+        (seed, epoch, rank) and is not part of it."""
+        step, draw = self.cursor_state()
+        return dict(seed=self.seed, seed64=self.seed64, step=step, draw=draw,
+                    noise_seed=[getattr(r, "noise_seed", None) for r in (self.res, self.res_init) if r is not None])
+
+    def load_state(self, st):
+        """Restores `state()` in place: the cursor keeps its address (a captured step goes on reading it), and the noise seed
+        goes to the resident datasets as in the constructor."""
+        self.seed, self.seed64 = int(st["seed"]), int(st["seed64"])
+        self._push_noise_seed()
+        self.set_cursor(int(st["step"]), int(st["draw"]))
+
     def start_epoch(self, epoch, table=None):
         """Uploads the epoch's table (one H2D copy into the fixed buffer) and rewinds the cursor's step; the draw goes on."""
         tab = self.build_table(epoch) if table is None else table.to(torch.int32)

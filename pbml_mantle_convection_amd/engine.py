@@ -570,6 +570,7 @@ class Engine:
         self.has_drop = any(n.kind == "conv" and n.drop > 0 for n in graph.nodes)
         self.drop_state = None
         self._drop_seed = 0
+        self._drop_step = 0                  # a step set before configure() allocated drop_state: written there
         self._drop_on = False                # whether the last forward ran with dropout (its backward follows it)
 
     # -------------------------------------------------------------- dropout state
@@ -579,6 +580,7 @@ class Engine:
         self._write_drop_state(0)
 
     def _write_drop_state(self, step: int):
+        self._drop_step = 0 if self.drop_state is not None else int(step) & 0xFFFFFFFF
         if self.drop_state is not None:
             host = np.array([self._drop_seed & 0xFFFFFFFF, self._drop_seed >> 32, int(step) & 0xFFFFFFFF, 0], dtype=np.uint32)
             self.drop_state.copy_(torch.from_numpy(host.view(np.int32)))
@@ -586,12 +588,17 @@ class Engine:
     def dropout_step(self) -> int:
         """The device step counter: the number of training-mode forwards since the seed was set (host sync)."""
         if self.drop_state is None:
-            return 0
+            return self._drop_step
         return int(self.drop_state[2].item()) & 0xFFFFFFFF
 
     def set_dropout_step(self, step: int):
-        """Rewind / set the step counter (the trainer restores it after the warm-up pass of a graph capture)."""
+        """Rewind / set the step counter (the trainer restores it after the warm-up pass of a graph capture).  Before the
+        engine is planned the step is kept and written when configure() allocates the device state."""
         self._write_drop_state(step)
+
+    def dropout_seed(self) -> int:
+        """The 64-bit seed as set (the device state holds its two words)."""
+        return self._drop_seed
 
     def _drop_desc(self, node):
         """mc_dropout of a node in a dropout pass, else None."""
@@ -697,7 +704,7 @@ class Engine:
         self.gmean = torch.empty((N, g.c_out), **f32) if g.subtract_mean else None
         if self.has_drop:
             self.drop_state = torch.zeros(4, dtype=torch.int32, device=device)
-            self._write_drop_state(0)
+            self._write_drop_state(self._drop_step)      # (0 unless a restored step waited for this allocation)
         self.shape = (N, H, W, str(device))
 
     def _plan_gn(self, e, node, o, f32):

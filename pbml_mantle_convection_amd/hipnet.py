@@ -60,6 +60,7 @@ class HipNetMixin:
         self._engines: Dict[str, Engine] = {}
         self._fwd_version = 0
         self._drop_seed = getattr(self, "_drop_seed", None)
+        self._drop_step = getattr(self, "_drop_step", 0)         # the step of a restored run (set_dropout_state), else 0
         self._pnames: List[str] = []
 
     @property
@@ -78,15 +79,39 @@ class HipNetMixin:
         e = self._engines.get(self._precision)
         if e is None:
             e = self._engines[self._precision] = Engine(self._graph, self._precision)
-            e.set_dropout_seed(torch.initial_seed() if self._drop_seed is None else self._drop_seed)
+            self.seed_engine(e)
         return e
+
+    def seed_engine(self, e: Engine):
+        """This module's dropout seed, and a restored step (set_dropout_state), for an engine created after they were set.
+        The step is the one that was restored, NOT the count the module's other engines have reached since: engines count
+        their own training-mode forwards (a new engine started at 0 before there was a restored step, and still does
+        without one), so an engine that is created after further training steps and must continue another engine's count
+        has to be given `set_dropout_step(other.dropout_step())` by its owner."""
+        e.set_dropout_seed(torch.initial_seed() if self._drop_seed is None else self._drop_seed)
+        if self._drop_step:
+            e.set_dropout_step(self._drop_step)
 
     def set_dropout_seed(self, seed: int):
         """Seed of the dropout masks (64 bits) for every engine of this module, present and future; the step counter
         restarts at 0.  The mask of a training-mode forward is a pure function of (seed, step, layer, element)."""
         self._drop_seed = int(seed)
+        self._drop_step = 0
         for e in self._engines.values():
             e.set_dropout_seed(self._drop_seed)
+        return self
+
+    def dropout_seed(self) -> int:
+        """The 64-bit seed the engines draw their masks from."""
+        return int(torch.initial_seed() if self._drop_seed is None else self._drop_seed) & 0xFFFFFFFFFFFFFFFF
+
+    def set_dropout_state(self, seed: int, step: int):
+        """Seed and step counter together (a restored run): written into every engine that exists, in place where its
+        device state is allocated, kept pending where it is not, and given to every engine created later."""
+        self.set_dropout_seed(seed)
+        self._drop_step = int(step) & 0xFFFFFFFF
+        for e in self._engines.values():
+            e.set_dropout_step(self._drop_step)
         return self
 
     def _named_hip_params(self):

@@ -97,6 +97,69 @@ def dropout_seed(seed: int, rank: int = 0, epoch: int = 0) -> int:
     return ((int(epoch) & 0xFFFFFFFF) << 32) | ((int(seed) + int(rank)) & 0xFFFFFFFF)
 
 
+# --------------------------------------------------------------------------------------------------
+# run state: everything the next epoch depends on that is not a pure function of the command line
+# --------------------------------------------------------------------------------------------------
+STATE_VERSION = 1
+STATE_FILE = "fluidnet_state.pt"
+
+
+def host_rng_state():
+    """The three host RNG streams the DataLoader path draws from (torch: the shuffle; Python `random` and numpy.random: the
+    datasets), as tensors and plain numbers so that the file loads with weights_only=True."""
+    ver, words, gauss = random.getstate()
+    name, keys, pos, has_gauss, cached = np.random.get_state()
+    return dict(torch=torch.get_rng_state().clone(),
+                python=dict(version=int(ver), words=torch.tensor(words, dtype=torch.int64), gauss=gauss),
+                numpy=dict(name=str(name), keys=torch.from_numpy(keys.astype(np.int64)), pos=int(pos), has_gauss=int(has_gauss),
+                           cached=float(cached)))
+
+
+def set_host_rng_state(st):
+    p, n = st["python"], st["numpy"]
+    random.setstate((int(p["version"]), tuple(int(w) for w in p["words"].tolist()), p["gauss"]))
+    np.random.set_state((n["name"], n["keys"].numpy().astype(np.uint32), int(n["pos"]), int(n["has_gauss"]), float(n["cached"])))
+    torch.set_rng_state(st["torch"].to(torch.uint8).cpu())
+
+
+def _is_plain(v):
+    """True for what a state file may hold: tensors, numbers, strings, None, and lists / tuples / dicts of them."""
+    if isinstance(v, dict):
+        return all(isinstance(k, (str, int)) and _is_plain(x) for k, x in v.items())
+    if isinstance(v, (list, tuple)):
+        return all(_is_plain(x) for x in v)
+    return v is None or isinstance(v, (bool, int, float, str, torch.Tensor))
+
+
+def write_state_file(state, path):
+    """torch.save to a temporary name in the same directory, then os.replace: the file at `path` is always a whole one, and a
+    failed write leaves the previous file and no temporary file behind."""
+    tmp = f"{path}.tmp{os.getpid()}"
+    try:
+        torch.save(state, tmp)
+        os.replace(tmp, path)
+    finally:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+
+
+def read_state_file(path):
+    return torch.load(path, map_location="cpu", weights_only=True)
+
+
+def restart_decision(state_epoch, log_epoch):
+    """How a `restart=True` run continues (pure): `state_epoch` is the epoch in the state file's header, None without a file;
+    `log_epoch` the last epoch of the text log.  Returns (exact, message): exact = load the whole state and continue bit for
+    bit; otherwise the weights-only restart, silent without a file, with one line to print when the two epochs disagree (a run
+    killed between the two writes)."""
+    if state_epoch is None:
+        return False, None
+    if int(state_epoch) == int(log_epoch):
+        return True, None
+    return False, (f"[mantle] {STATE_FILE} holds epoch {int(state_epoch)}, the log ends at epoch {int(log_epoch)}: restarting "
+                   f"from the weights of epoch {int(log_epoch)} alone (optimizer state, seeds and counters start afresh)")
+
+
 class Trainer:
     _promotion_logged = False
 
@@ -104,7 +167,8 @@ class Trainer:
                  optimizer: torch.optim.Optimizer, scheduler, gpu_id: int, save_every: int, nn_dir, p_pred=False,
                  debug=False, network="fluidnet", loss_scale=False, loss_derivative=False, roll_forward=1, epoch=0,
                  loss_type="curl", *, norm="l1", lambda_mom=0.0, precision=None, use_graph=False, log_every=100,
-                 drop_seed=None, max_grad_norm: float = 0.0, skip_nonfinite: bool = False, max_skipped_in_a_row: int = 50):
+                 drop_seed=None, max_grad_norm: float = 0.0, skip_nonfinite: bool = False, max_skipped_in_a_row: int = 50,
+                 save_state: bool = False):
         if network not in ("unet", "iunet", "convae", "newfluidnet", "fluidnet", "ifluidnet"):
             raise NotImplementedError(f"network={network!r}: the HIP path covers 'unet' / 'iunet', 'convae', 'newfluidnet' and "
                                       "'fluidnet' / 'ifluidnet'")
@@ -135,6 +199,7 @@ class Trainer:
         self.loss_scale, self.loss_derivative, self.roll_forward = loss_scale, loss_derivative, roll_forward
         self.start_epoch, self.loss_type = epoch, loss_type
         self.use_graph, self.log_every = use_graph, log_every
+        self.save_state, self.epoch_done = bool(save_state), int(epoch) - 1
         # flat parameter / gradient / Adam-moment buffers; nn.Parameters become views
         self.flat = FlatParams(self.model_uvp, self.device)
         self.exp_avg = torch.zeros_like(self.flat.param)
@@ -447,6 +512,7 @@ class Trainer:
                 lo = copy.copy(self.loss)
                 lo._shape, lo._frozen = None, False
                 self._eval_pair = (Engine(self.model_uvp._graph, self.model_uvp.precision), lo)
+                self.model_uvp.seed_engine(self._eval_pair[0])      # (it never draws a mask: evaluation runs without dropout)
             return self._fwd_bwd(gVTp, uvp, yc, paras, scaler, train=False, eng=self._eval_pair[0], loss=self._eval_pair[1])
         return self._fwd_bwd(gVTp, uvp, yc, paras, scaler, train=False)
 
@@ -572,6 +638,142 @@ class Trainer:
                   f"non-finite gradients ({rec['skipped']} since the start)", flush=True)
             self._skipped_seen = rec["skipped"]
 
+    # ------------------------------------------------------------------ run state
+    def _loaders(self):
+        return {k: ld for k, ld in (("train_data", self.train_data), ("cv_data", self.cv_data))
+                if isinstance(ld, ResidentLoader)}                                      # noqa: F405
+
+    def rank_state(self):
+        """This rank's entry of the state: dropout seed and step, the resident loaders' seeds and cursors, the host RNG streams."""
+        m = self.model_uvp
+        has = hasattr(m, "set_dropout_state")
+        return dict(drop_seed=m.dropout_seed() if has else int(self.drop_seed), drop_step=m.engine().dropout_step() if has else 0,
+                    loaders={k: ld.state() for k, ld in self._loaders().items()}, rng=host_rng_state())
+
+    def gather_rank_states(self):
+        """Every rank's entry, in rank order.  With world > 1 this is ONE all_gather_object: every rank must call it."""
+        mine = self.rank_state()
+        if self.world == 1:
+            return [mine]
+        out = [None] * self.world
+        dist.all_gather_object(out, mine)
+        return out
+
+    def _layout(self):
+        f = self.flat
+        return dict(names=list(f.names), shapes=[list(s) for s in f.shapes], offsets=[int(o) for o in f.offsets])
+
+    def state_dict(self, ranks=None):
+        """The whole training state after the last finished epoch as a plain dict (CPU tensors, numbers, strings, nested
+        dicts and lists): header, layout of the flat buffer, optimizer (f32 masters, both Adam moments, step count, the param
+        group's scalars, the scheduler), the guard record, and one entry per rank.  `ranks`: the result of
+        gather_rank_states(); left out, it is gathered here -- a collective with world > 1.  Not an nn.Module method."""
+        ranks = self.gather_rank_states() if ranks is None else ranks
+        g = self.optimizer.param_groups[0]
+        b1, b2, eps, wd = self._adam_args()
+        sch = {}
+        for k, v in self.scheduler.state_dict().items():              # (MultiStepLR keeps its milestones in a Counter)
+            sch[k] = dict(counter=sorted(v.elements())) if hasattr(v, "elements") else v
+            if not _is_plain(sch[k]):                                  # said here, not as an unpickling error at the next restart
+                raise TypeError(f"scheduler.state_dict()[{k!r}] is a {type(v).__name__}: the run state holds tensors, numbers, "
+                                "strings, lists and dicts only (it is read with weights_only=True)")
+        return dict(                                                   # (the .cpu() copies are the device sync)
+            header=dict(version=STATE_VERSION, epoch=int(self.epoch_done), world=int(self.world),
+                        precision=str(self.model_uvp.precision), network=str(self.net), numel=int(self.flat.numel)),
+            layout=self._layout(),
+            optimizer=dict(param=self.flat.param.detach().cpu(), exp_avg=self.exp_avg.cpu(), exp_avg_sq=self.exp_avg_sq.cpu(),
+                           step_count=self.step_count.cpu(), lr=float(g["lr"]), betas=[b1, b2], eps=eps, weight_decay=wd,
+                           scheduler=sch),
+            guard=dict(record=None if self._guard is None else self._guard.cpu(), skipped_seen=int(self._skipped_seen)),
+            ranks=ranks)
+
+    def _check_state(self, state):
+        h = state["header"]
+        if h["version"] != STATE_VERSION:
+            raise ValueError(f"run state of format version {h['version']}; this build reads version {STATE_VERSION}")
+        mine = dict(world=int(self.world), precision=str(self.model_uvp.precision), network=str(self.net))
+        for k, v in mine.items():
+            if h[k] != v:
+                raise ValueError(f"run state was written with {k}={h[k]!r}, this run has {k}={v!r}: it cannot continue exactly")
+        a, b = state["layout"], self._layout()
+        for i, (n0, s0, o0) in enumerate(zip(a["names"], a["shapes"], a["offsets"])):
+            if i >= len(b["names"]):
+                break
+            n1, s1, o1 = b["names"][i], b["shapes"][i], b["offsets"][i]
+            if (n0, list(s0), int(o0)) != (n1, s1, o1):
+                raise ValueError(f"run state and model differ at parameter {i}: the state holds {n0!r} of shape {tuple(s0)} at "
+                                 f"offset {int(o0)}, the model {n1!r} of shape {tuple(s1)} at offset {o1}")
+        if len(a["names"]) != len(b["names"]) or int(h["numel"]) != self.flat.numel:
+            raise ValueError(f"run state holds {len(a['names'])} parameters in {int(h['numel'])} floats, the model "
+                             f"{len(b['names'])} in {self.flat.numel}")
+        has = state["guard"]["record"] is not None
+        if has != (self._guard is not None):
+            raise ValueError(f"run state was written with a gradient guard {'on' if has else 'off'}, this run has it "
+                             f"{'on' if self._guard is not None else 'off'}")
+        if len(state["ranks"]) != self.world:
+            raise ValueError(f"run state holds {len(state['ranks'])} per-rank entries, this run has world={self.world}")
+        mine = state["ranks"][dist.get_rank() if self.world > 1 else 0]
+        if set(mine["loaders"]) != set(self._loaders()):
+            raise ValueError(f"run state holds resident loaders {sorted(mine['loaders'])}, this run has {sorted(self._loaders())}")
+        if self._graph is not None:
+            # a captured step holds these as launch arguments: a state that changes them cannot be replayed by this graph
+            o = state["optimizer"]
+            new = (float(o["betas"][0]), float(o["betas"][1]), float(o["eps"]), float(o["weight_decay"]))
+            if new != self._adam_args():
+                raise ValueError(f"run state has Adam (betas, eps, weight_decay) = {new}, the captured step was recorded with "
+                                 f"{self._adam_args()}")
+            for k, ld in self._loaders().items():
+                if int(mine["loaders"][k]["seed64"]) != ld.seed64:
+                    raise ValueError(f"run state has noise seed {int(mine['loaders'][k]['seed64'])} for {k}, the captured step "
+                                     f"was recorded with {ld.seed64}")
+
+    def load_state_dict(self, state):
+        """Restores `state_dict()` IN PLACE: flat.param, both moments, step_count, the guard record and the loader cursors keep
+        their addresses, the nn.Parameter views stay bound, and a step graph captured earlier goes on replaying correctly.  The
+        optimizer's lr and the scheduler are restored (the next step's _sync_lr picks the rate up); the three host RNG streams
+        come last.  Raises ValueError, before anything is written, for a state that cannot continue exactly: another format
+        version, world, precision, network, or layout of the flat buffer."""
+        self._check_state(state)
+        o = state["optimizer"]
+        with torch.no_grad():
+            self.flat.param.copy_(o["param"])
+            self.exp_avg.copy_(o["exp_avg"])
+            self.exp_avg_sq.copy_(o["exp_avg_sq"])
+            self.step_count.copy_(o["step_count"].to(torch.int32))
+            if self._guard is not None:
+                self._guard.copy_(state["guard"]["record"].to(torch.int32))
+        self._skipped_seen = int(state["guard"]["skipped_seen"])
+        g = self.optimizer.param_groups[0]
+        g["lr"], g["betas"], g["eps"], g["weight_decay"] = float(o["lr"]), (float(o["betas"][0]), float(o["betas"][1])), \
+            float(o["eps"]), float(o["weight_decay"])
+        live = self.scheduler.state_dict()
+        sch = {}
+        for k, v in o["scheduler"].items():
+            if isinstance(v, dict) and set(v) == {"counter"}:
+                v = type(live[k])(v["counter"]) if k in live and hasattr(live[k], "elements") else list(v["counter"])
+            sch[k] = v
+        self.scheduler.load_state_dict(sch)
+        self.epoch_done = int(state["header"]["epoch"])
+        mine = state["ranks"][dist.get_rank() if self.world > 1 else 0]
+        self.drop_seed = int(mine["drop_seed"])
+        if hasattr(self.model_uvp, "set_dropout_state"):
+            self.model_uvp.set_dropout_state(self.drop_seed, int(mine["drop_step"]))
+            if getattr(self, "_eval_pair", None) is not None:
+                self.model_uvp.seed_engine(self._eval_pair[0])
+        for k, ld in self._loaders().items():
+            ld.load_state(mine["loaders"][k])
+        set_host_rng_state(mine["rng"])
+
+    def load_state(self, state):
+        """Continue a run from its state file (a path, or the dict read from it): load_state_dict, then the scheduler step of
+        the state's epoch -- the file is written before train() steps the scheduler for that epoch -- and the run goes on at
+        epoch + 1."""
+        if not isinstance(state, dict):
+            state = read_state_file(state)
+        self.load_state_dict(state)
+        self.scheduler.step()
+        self.start_epoch = self.epoch_done + 1
+
     def _save_checkpoint(self, epoch):
         """File names, state_dict keys and the log line format of the reference (:412-436)."""
         ckp = {k: v.detach().clone() for k, v in self.model_uvp.state_dict().items()}
@@ -594,7 +796,13 @@ class Trainer:
             self.losses_cv = [0.0] * 6
             self._run_epoch(epoch)
             t1 = time.time()
+            self.epoch_done = epoch
+            ranks = None
+            if self.save_state and epoch % self.save_every == 0:
+                ranks = self.gather_rank_states()      # a collective: here, where EVERY rank passes, not on rank 0's path below
             if (self.gpu_id == 0 or self.world == 1) and epoch % self.save_every == 0:
+                if self.save_state:                    # before the weights file and the log line: one file, replaced atomically
+                    write_state_file(self.state_dict(ranks), self.nn_dir + STATE_FILE)
                 self._save_checkpoint(epoch)
                 print(t1 - t0)
             self.scheduler.step()          # on EVERY rank (reference: rank 0 only -> diverging LRs)
@@ -723,7 +931,7 @@ def main(rank: int, world_size: int, save_every: int, total_epochs: int, batch_s
          restart=False, advect=False, network="fluidnet", debug=False, scale=True, blurr=False, master_port=366,
          l2_reg=0.0, dropout=0.0, loss_scale=False, loss_derivative=False, roll_forward=1, factor=2, multi_scales=[],
          synthetic=None, precision=None, lambda_mom=0.0, use_graph=False, clip_norm=0.0, skip_nonfinite=False, noise=0.0,
-         resident=False):
+         resident=False, save_state=False):
     if resident and synthetic is not None:
         raise ValueError("--resident 1 keeps shard-file datasets in HBM; the --synthetic set has no shard files (leave "
                          "--resident at 0 with --synthetic)")
@@ -743,7 +951,17 @@ def main(rank: int, world_size: int, save_every: int, total_epochs: int, batch_s
     trainer = Trainer(model_uvp, model_AD, train_data, cv_data, None, None, optimizer, scheduler, rank, save_every,
                       nn_dir, p_pred, debug, network, loss_scale, loss_derivative, roll_forward, epoch=epoch,
                       loss_type=loss_type, precision=precision, lambda_mom=lambda_mom, use_graph=use_graph,
-                      max_grad_norm=clip_norm, skip_nonfinite=skip_nonfinite)
+                      max_grad_norm=clip_norm, skip_nonfinite=skip_nonfinite, save_state=save_state)
+    if restart:
+        # exact restart when the run left a state file of the log's last epoch; otherwise the weights-only restart that
+        # load_train_objs has already set up (its start rate and rebased milestones are overridden by the state's scheduler)
+        path = nn_dir + STATE_FILE
+        state = read_state_file(path) if os.path.exists(path) else None
+        exact, message = restart_decision(None if state is None else state["header"]["epoch"], epoch - 1)
+        if message is not None and rank == 0:                  # one line per run, not one per rank
+            print(message, flush=True)
+        if exact:
+            trainer.load_state(state)
     trainer.train(total_epochs)
     if dist.is_initialized():
         dist.destroy_process_group()
@@ -794,6 +1012,7 @@ def build_arg_parser():
     p.add_argument("--clip_norm", type=float, default=0.0)        # global gradient-norm clip (0 = off)
     p.add_argument("--skip_nonfinite", type=int, default=0)       # 1: skip the optimizer step of a non-finite gradient
     p.add_argument("--resident", type=int, default=0)             # 1: datasets resident in HBM, batches assembled inside the step
+    p.add_argument("--save_state", type=int, default=0)           # 1: write the whole training state beside the weights; -rst 1 then resumes bit for bit
     return p
 
 
@@ -872,7 +1091,7 @@ def cli(argv=None):
             a.use_skip == 1, p_pred, a.spectral_conv == 1, a.dilation, a.a_bound, a.restart == 1, a.advect == 1,
             a.network, debug, a.scale == 1, a.blurr == 1, a.master_port, a.l2_reg, a.drop_rate, a.loss_scale == 1,
             a.loss_derivative == 1, a.roll_forward, a.factor, a.multi_scales, synthetic, a.precision, a.lambda_mom,
-            a.use_graph == 1, a.clip_norm, a.skip_nonfinite == 1, a.noise, a.resident == 1)
+            a.use_graph == 1, a.clip_norm, a.skip_nonfinite == 1, a.noise, a.resident == 1, a.save_state == 1)
     if world_size == 1:
         main(0, *args)
     else:
