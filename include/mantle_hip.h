@@ -179,6 +179,16 @@ int mc_conv2d_wgrad_finalize(const mc_conv_desc* d, const void* partials, float*
 /* mc_conv2d_wgrad with x0 / x1 given as RAW conv outputs: the activation is re-applied on load (pro as in mc_conv2d_fused). */
 int mc_conv2d_wgrad_fused(const mc_conv_desc* d, const void* x0, const void* x1, const mc_conv_prologue* pro,
                           const void* dy, void* partials, void* stream);
+/* mc_conv2d_wgrad for a conv -> GroupNorm -> act layer whose dz = dA act'(z) exists (mc_conv2d_fused's epilogue +
+ * mc_fold_padded_dz) but whose dy does not: the launch forms dy = cA dz + (cB (y - mean) + cC) -- the value mc_gn_bwd_apply_dz
+ * writes, bit for bit -- while it stages its tiles, accumulates the filter gradient of that dy and stores dy (bf16 CB8
+ * [n][ceil(c_out/8)][ho][wo][8]) for the input-gradient launch that follows.  dz: MC_GSRC_PADFOLD or MC_GSRC_PLAIN of the
+ * layer's output shape; y: the layer's raw conv output (f16); dz_coef: [n][ceil(c_out/8)*8][4] f32 = (cA, cB, cC, mean) from
+ * mc_gn_act_bwd_finalize_dz / _n_dz, zeros in padded channels.  partials and mc_conv2d_wgrad_finalize as for mc_conv2d_wgrad
+ * (the same slabs).  MC_EUNSUPPORTED unless dtype == MC_MIX16, the padded input channels fill at most 16 and c_out <= 16
+ * (each dy tile is then staged by exactly one work-group), and dz has the layer's output shape. */
+int mc_conv2d_wgrad_dz(const mc_conv_desc* d, const void* x0, const void* x1, const mc_grad_src* dz, const void* y,
+                       const float* dz_coef, void* dy, void* partials, void* stream);
 /* Batched forms (one launch for many layers; per-layer tables are plain host arrays of length n):
  * the per-step bank packing and the filter-gradient combine are tiny per layer and latency-bound when
  * launched one layer at a time. */
@@ -247,6 +257,15 @@ int mc_gn_act_bwd_finalize(const float* partials, int32_t n, int32_t blocks, int
  * mc_gn_param_grads_batched (samples in order: deterministic).  Channels per group: 1, 2, 4 or 8. */
 int mc_gn_act_bwd_finalize_n(const float* partials, int32_t n, int32_t blocks, int32_t c, int32_t groups, int32_t hw,
                              const float* gamma, float* m12_ng2, float* chan_sums, void* stream);
+/* The two finalize forms, writing in addition the table mc_conv2d_wgrad_dz reads: dz_coef [n][c8*8][4] = (cA, cB, cC, mean)
+ * per (sample, channel) from coef (the layer's (scale, shift, mean, rstd) table) and the m12 just computed; rows of padded
+ * channels are not written (allocate the table zeroed).  m12_ng2 is required. */
+int mc_gn_act_bwd_finalize_dz(const float* partials, int32_t n, int32_t blocks, int32_t c, int32_t groups, int32_t hw,
+                              const float* gamma, float* m12_ng2, float* dgamma, float* dbeta, const float* coef,
+                              float* dz_coef, void* stream);
+int mc_gn_act_bwd_finalize_n_dz(const float* partials, int32_t n, int32_t blocks, int32_t c, int32_t groups, int32_t hw,
+                                const float* gamma, float* m12_ng2, float* chan_sums, const float* coef, float* dz_coef,
+                                void* stream);
 int mc_gn_act_bwd_apply(const void* y, int32_t n, int32_t c, int32_t h, int32_t w, int32_t groups,
                         const float* stats_ng2, const float* m12_ng2, const float* gamma,
                         const float* beta, int32_t post, int32_t act, int32_t dtype,

@@ -114,6 +114,9 @@ SIGNATURES = {
     "mc_conv2d": (C.c_int, [_CD, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mc_conv2d_fused": (C.c_int, [_CD, _vp, _vp, _CP, _vp, _vp, _vp, _vp, _vp, _CE, _vp]),
     "mc_conv2d_wgrad_fused": (C.c_int, [_CD, _vp, _vp, _CP, _vp, _vp, _vp]),
+    "mc_conv2d_wgrad_dz": (C.c_int, [_CD, _vp, _vp, _GS, _vp, _vp, _vp, _vp, _vp]),
+    "mc_gn_act_bwd_finalize_dz": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mc_gn_act_bwd_finalize_n_dz": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mc_gn_finalize_coef": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp]),
     "mc_fold_blocks": (_i32, [_i32, _i32, _i32, _i32]),
     "mc_fold_padded_dz": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _i32, _i32, _vp]),

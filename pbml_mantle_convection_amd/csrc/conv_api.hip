@@ -12,6 +12,7 @@ int mc_conv2d_bf16(const ConvGeom& g, const void* x0, const void* x1, const void
                    void* y1, float* part, const ConvFuse& fz, int fuse, hipStream_t s);
 int mc_wgrad_bf16(const ConvGeom& g, const void* x0, const void* x1, const void* dy, void* part, const ConvFuse& fz, int fuse,
                   hipStream_t s);
+int mc_wgrad_dz_bf16(const ConvGeom& g, const void* x0, const void* x1, const WgradDz& zs, void* part, hipStream_t s);
 const char* mc_bf16_kernel_name(const ConvGeom& g);
 void mc_bf16_bank_dims(const ConvGeom& g, int dgrad, int& chunks, int& steps, int& ntiles);
 // row-reuse bf16 path for single-output-tile layers (conv_rr_bf16.hip)
@@ -316,6 +317,24 @@ int mc_conv2d_wgrad_fused(const mc_conv_desc* d, const void* x0, const void* x1,
   if (rc) return rc;
   if (mc_is16(g.dtype)) return mc_wgrad_bf16(g, x0, x1, dy, partials, fz, fuse, (hipStream_t)stream);
   return mc_wgrad_f32(g, x0, x1, dy, partials, fz, fuse, (hipStream_t)stream);
+}
+
+int mc_conv2d_wgrad_dz(const mc_conv_desc* d, const void* x0, const void* x1, const mc_grad_src* dz, const void* y,
+                       const float* dz_coef, void* dy, void* partials, void* stream) {
+  ConvGeom g;
+  int rc = geom_for(d, g);
+  if (rc) return rc;
+  if (!x0 || !dz || !dz->ptr || !y || !dz_coef || !dy || !partials || (g.Cin1 > 0 && !x1)) return MC_EINVAL;
+  // one input-channel chunk and one output-channel group: every dY tile is then staged, and so formed, exactly once
+  if (g.dtype != MC_MIX16 || g.CBin > 2 || g.Cout > 16) return MC_EUNSUPPORTED;
+  if (dz->kind != MC_GSRC_PADFOLD && dz->kind != MC_GSRC_PLAIN) return MC_EUNSUPPORTED;
+  if (dz->c8_total != 0 || dz->hs != g.Ho || dz->ws != g.Wo) return MC_EUNSUPPORTED;
+  const int zpad = dz->kind == MC_GSRC_PADFOLD ? dz->pad : 0;
+  if (zpad < 0 || zpad > 2) return MC_EUNSUPPORTED;
+  if ((size_t)g.CBout * g.Ho * g.Wo * 16 > 0x7fffffffu) return MC_EUNSUPPORTED;      // (32-bit offsets inside a sample)
+  WgradDz zs;
+  zs.dz = dz->ptr; zs.z = y; zs.coef = dz_coef; zs.dy = dy; zs.zpad = zpad;
+  return mc_wgrad_dz_bf16(g, x0, x1, zs, partials, (hipStream_t)stream);
 }
 
 int mc_conv2d_wgrad(const mc_conv_desc* d, const void* x0, const void* x1, const void* dy, void* partials,

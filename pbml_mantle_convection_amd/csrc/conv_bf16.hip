@@ -511,10 +511,18 @@ constexpr int WTH = 16, WTW = 32;      // work-item tile (output pixels)
 // they were equal (the filter gradients run on the side stream and are off the critical path).
 // PRO: x0 / x1 are raw conv outputs; the producer's GroupNorm affine + activation are applied while the tile is staged.
 // XH (MC_MIX16): x0 / x1 are f16 tensors of the forward pass, converted to bf16 while the tile is staged (dy is bf16).
-template <int K, int NTW, bool PRO = false, bool XH = false>
-__global__ __launch_bounds__(256, NTW == 1 ? 3 : 2) void k_wgrad_mfma_bf16(ConvGeom g, const bf16_t* __restrict__ x0,
-                                                            const bf16_t* __restrict__ x1, const bf16_t* __restrict__ dy,
-                                                            float* __restrict__ part, int tiles_x, int tiles, ConvFuse fz) {
+// DYZ (one chunk, one co-group: every dY tile is staged exactly once, by one block): dY does not exist yet.  prefetch() loads
+// the tile's dz through zs, commit() loads the f16 raw conv output z of the same slots (into registers the MFMA loop has
+// released), forms dY = cA dz + (cB (z - mean) + cC) -- k_gn_bwd_apply_dz's expression, operation for operation -- writes it
+// to the LDS tile and stores it to zs.dy for the input-gradient launch that follows: the apply launch and one read of dY go.
+#ifndef MC_WGRAD_DZ_WGS
+#define MC_WGRAD_DZ_WGS 3                    // resident work-groups per CU the DYZ instantiations are compiled for
+#endif
+template <int K, int NTW, bool PRO = false, bool XH = false, bool DYZ = false>
+__global__ __launch_bounds__(256, NTW == 1 ? (DYZ ? MC_WGRAD_DZ_WGS : 3) : 2) void k_wgrad_mfma_bf16(
+    ConvGeom g, const bf16_t* __restrict__ x0, const bf16_t* __restrict__ x1, const bf16_t* __restrict__ dy,
+    float* __restrict__ part, int tiles_x, int tiles, ConvFuse fz, WgradDz zs) {
+  static_assert(!DYZ || (NTW == 1 && XH && !PRO), "DYZ: MC_MIX16, one co-tile, sources read as they are");
   constexpr int NS = 4;                                         // tap groups = waves
   constexpr int TPW = (K * K + NS) / NS;                        // accumulator slots of a wave (last group: + bias)
   constexpr int KK = K * K;
@@ -590,10 +598,12 @@ __global__ __launch_bounds__(256, NTW == 1 ? 3 : 2) void k_wgrad_mfma_bf16(ConvG
   float psc[2][8], psh[2][8];
   int pact[2] = {-1, -1};
   unsigned okm = 0xffffffffu;
+  int z_n = 0, z_ty0 = 0, z_tx0 = 0;           // DYZ: the work item whose dz sits in rd (uniform)
   auto prefetch = [&](int wi_fwd) __attribute__((always_inline)) {
     const int wi = wi_fwd;
     const int n = wi / tiles, tile = wi - n * tiles;
     const int ty0 = (tile / tiles_x) * WTH, tx0 = (tile % tiles_x) * WTW;
+    if constexpr (DYZ) { z_n = n; z_ty0 = ty0; z_tx0 = tx0; }
     const bool interior = (ty0 - g.pad >= 0) && (ty0 - g.pad + TIH <= g.H) && (tx0 - g.pad >= 0) && (tx0 - g.pad + TIW <= g.W);
     const char* bpn[2] = {xbase[0] + (size_t)n * xC8[0] * g.H * g.W * 16, xbase[1] + (size_t)n * xC8[1] * g.H * g.W * 16};
     if constexpr (PRO) {
@@ -633,6 +643,29 @@ __global__ __launch_bounds__(256, NTW == 1 ? 3 : 2) void k_wgrad_mfma_bf16(ConvG
         }
       }
     }
+    if constexpr (DYZ) {
+      // dz on the (padded) domain of the consumer's input gradient: same slots, same zero fill
+      const int zp = zs.zpad, Hz = g.Ho + 2 * zp, Wz = g.Wo + 2 * zp;
+      const bf16_t* zb = reinterpret_cast<const bf16_t*>(zs.dz);
+      if (co_full && ty0 + WTH <= g.Ho && tx0 + WTW <= g.Wo) {
+        const char* db = reinterpret_cast<const char*>(zb) + cb8_index(n, cog * NTW * 2, ty0 + zp, tx0 + zp, g.CBout, Hz, Wz) * sizeof(bf16_t);
+        const unsigned d_offz = (unsigned)(d_r0 * Wz + d_c0) * 16u;
+#pragma unroll
+        for (int it = 0; it < D_ITERS; ++it)
+          rd[it] = *reinterpret_cast<const uint4*>(db + (size_t)((it >> 1) * Hz + 8 * (it & 1)) * Wz * 16 + d_offz);
+        return;
+      }
+#pragma unroll
+      for (int it = 0; it < D_ITERS; ++it) {
+        const int cob = (cog * NTW) * 2 + (it >> 1);
+        const int oy = ty0 + d_r0 + 8 * (it & 1), ox = tx0 + d_c0;
+        const bool ok = cob < g.CBout && oy < g.Ho && ox < g.Wo;
+        uint4 v = *reinterpret_cast<const uint4*>(zb + cb8_index(n, min(cob, g.CBout - 1), min(oy, g.Ho - 1) + zp,
+                                                                 min(ox, g.Wo - 1) + zp, g.CBout, Hz, Wz));
+        rd[it] = ok ? v : make_uint4(0, 0, 0, 0);
+      }
+      return;
+    }
     if (co_full && ty0 + WTH <= g.Ho && tx0 + WTW <= g.Wo) {
       const char* db = reinterpret_cast<const char*>(dy) + cb8_index(n, cog * NTW * 2, ty0, tx0, g.CBout, g.Ho, g.Wo) * sizeof(bf16_t);
 #pragma unroll
@@ -655,6 +688,21 @@ __global__ __launch_bounds__(256, NTW == 1 ? 3 : 2) void k_wgrad_mfma_bf16(ConvG
     }
   };
   auto commit = [&]() __attribute__((always_inline)) {
+    // DYZ: z of this thread's dy slots, issued first so that the conversion of x below covers part of the latency
+    uint4 rz[DYZ ? D_ITERS : 1];
+    unsigned z_off[DYZ ? D_ITERS : 1];
+    unsigned z_ok = 0;
+    if constexpr (DYZ) {
+      const char* zb = reinterpret_cast<const char*>(zs.z) + (size_t)z_n * g.CBout * g.Ho * g.Wo * 16;
+#pragma unroll
+      for (int it = 0; it < D_ITERS; ++it) {
+        const int cob = (cog * NTW) * 2 + (it >> 1);
+        const int oy = z_ty0 + d_r0 + 8 * (it & 1), ox = z_tx0 + d_c0;
+        if (cob < g.CBout && oy < g.Ho && ox < g.Wo) z_ok |= 1u << it;
+        z_off[it] = (unsigned)((min(cob, g.CBout - 1) * g.Ho + min(oy, g.Ho - 1)) * g.Wo + min(ox, g.Wo - 1)) * 16u;
+        rz[it] = *reinterpret_cast<const uint4*>(zb + z_off[it]);
+      }
+    }
 #pragma unroll
     for (int cb = 0; cb < 2; ++cb)
 #pragma unroll
@@ -673,8 +721,39 @@ __global__ __launch_bounds__(256, NTW == 1 ? 3 : 2) void k_wgrad_mfma_bf16(ConvG
           xs[cb * XPS + ((v >> 15) & 0x7fff) * XRS + (v & 0x7fff)] = q;
         }
       }
+    if constexpr (DYZ) {
+      char* const ob = reinterpret_cast<char*>(zs.dy) + (size_t)z_n * g.CBout * g.Ho * g.Wo * 16;
+      __builtin_amdgcn_sched_barrier(0);         // x is in LDS: its staging registers are free from here on
 #pragma unroll
-    for (int it = 0; it < D_ITERS; ++it) ds[d_lds0 + (it >> 1) * DPS + 8 * (it & 1) * DRS] = rd[it];
+      for (int it = 0; it < D_ITERS; ++it) {
+        // (cA, cB, cC, mean) of the plane's 8 channels for this sample: uniform, and written by an earlier launch only, so
+        // they are read as constant memory (scalar loads; as plain global loads they are vector loads, because the kernel
+        // itself stores to global memory, and every slot waits for eight of them)
+        typedef const __attribute__((address_space(4))) f32x4 cf32x4;
+        cf32x4* ct = (cf32x4*)(reinterpret_cast<const f32x4*>(zs.coef) + (size_t)z_n * g.CoutP + min((cog * NTW) * 2 + (it >> 1), g.CBout - 1) * 8);
+        float v[8], dz[8], o[8];
+        V8<f16_t>::ld(reinterpret_cast<const f16_t*>(&rz[it]), v);
+        V8<bf16_t>::ld(reinterpret_cast<const bf16_t*>(&rd[it]), dz);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) dz[j] = 0.f + dz[j];          // the apply kernel accumulates its source onto +0 (a -0 becomes +0)
+#pragma unroll
+        for (int j = 0; j < 8; j += 2) {
+          const f32x4 c0 = ct[j], c1 = ct[j + 1];
+          const f32x2 t = (f32x2){v[j], v[j + 1]} - (f32x2){c0.w, c1.w};
+          const f32x2 r = pk_fma((f32x2){c0.x, c1.x}, (f32x2){dz[j], dz[j + 1]}, pk_fma((f32x2){c0.y, c1.y}, t, (f32x2){c0.z, c1.z}));
+          o[j] = r.x; o[j + 1] = r.y;
+        }
+        uint4 q = make_uint4(pk_bf16(o[0], o[1]), pk_bf16(o[2], o[3]), pk_bf16(o[4], o[5]), pk_bf16(o[6], o[7]));
+        const bool ok = (z_ok >> it) & 1u;
+        if (!ok) q = make_uint4(0, 0, 0, 0);                       // outside the image / beyond CBout: zero in the tile, not stored
+        ds[d_lds0 + (it >> 1) * DPS + 8 * (it & 1) * DRS] = q;
+        if (ok) *reinterpret_cast<uint4*>(ob + z_off[it]) = q;
+        __builtin_amdgcn_sched_barrier(0);       // one slot at a time: four slots' unpacked values at once do not fit (spills)
+      }
+    } else {
+#pragma unroll
+      for (int it = 0; it < D_ITERS; ++it) ds[d_lds0 + (it >> 1) * DPS + 8 * (it & 1) * DRS] = rd[it];
+    }
   };
 
   f32x4 acc[NACC];
@@ -888,7 +967,7 @@ int mc_wgrad_bf16(const ConvGeom& g_in, const void* x0, const void* x1, const vo
   const bool xh = g.dtype == MC_MIX16;
 #define WLAUNCH_X(K, NTW, PRO, XH)                                                                                     \
   hipLaunchKernelGGL((k_wgrad_mfma_bf16<K, NTW, PRO, XH>), grid, dim3(256), 0, s, g, (const bf16_t*)x0, (const bf16_t*)x1, \
-                     (const bf16_t*)dy, (float*)part, tiles_x, tiles, fz)
+                     (const bf16_t*)dy, (float*)part, tiles_x, tiles, fz, WgradDz{})
 #define WLAUNCH_P(K, NTW, PRO) do { if (xh) WLAUNCH_X(K, NTW, PRO, true); else WLAUNCH_X(K, NTW, PRO, false); } while (0)
 #define WLAUNCH(K, NTW) do { if (fuse) WLAUNCH_P(K, NTW, true); else WLAUNCH_P(K, NTW, false); } while (0)
   if (g.K == 5) { if (ntw == 1) WLAUNCH(5, 1); else WLAUNCH(5, 2); }
@@ -897,6 +976,23 @@ int mc_wgrad_bf16(const ConvGeom& g_in, const void* x0, const void* x1, const vo
 #undef WLAUNCH
 #undef WLAUNCH_P
 #undef WLAUNCH_X
+  MC_CHECK_LAUNCH();
+  return MC_OK;
+}
+
+// The DYZ form (see k_wgrad_mfma_bf16): dY is formed from (dz, z, coefficient table) while the tile is staged and stored to
+// zs.dy.  One input-channel chunk and one co-group only, so that every dY tile is staged by exactly one block.
+int mc_wgrad_dz_bf16(const ConvGeom& g, const void* x0, const void* x1, const WgradDz& zs, void* part, hipStream_t s) {
+  const int tiles_x = (g.Wo + WTW - 1) / WTW, tiles_y = (g.Ho + WTH - 1) / WTH;
+  const int tiles = tiles_x * tiles_y;
+  if (g.dtype != MC_MIX16 || g.CBin > 2 || g.Cout > 16) return MC_EUNSUPPORTED;
+  dim3 grid(g.wgrad_G, 1, 1);
+  const ConvFuse fz = conv_fuse_none();
+#define WLAUNCH_DZ(K)                                                                                                  \
+  hipLaunchKernelGGL((k_wgrad_mfma_bf16<K, 1, false, true, true>), grid, dim3(256), 0, s, g, (const bf16_t*)x0,       \
+                     (const bf16_t*)x1, (const bf16_t*)nullptr, (float*)part, tiles_x, tiles, fz, zs)
+  if (g.K == 5) WLAUNCH_DZ(5); else if (g.K == 3) WLAUNCH_DZ(3); else return MC_EUNSUPPORTED;
+#undef WLAUNCH_DZ
   MC_CHECK_LAUNCH();
   return MC_OK;
 }

@@ -38,6 +38,16 @@ static inline ConvFuse conv_fuse_none() {
   return f;
 }
 
+// What the DYZ form of the 16-bit filter-gradient kernel (mc_conv2d_wgrad_dz) reads instead of dY, and where it leaves the dY
+// it forms: dY = cA dz + (cB (z - mean) + cC), the expression of k_gn_bwd_apply_dz, per (sample, channel).
+struct WgradDz {
+  const void* dz;       // bf16 CB8 [N][CBout][Ho + 2 zpad][Wo + 2 zpad], read at offset (zpad, zpad)
+  const void* z;        // f16 CB8 [N][CBout][Ho][Wo]: the layer's raw conv output
+  const float* coef;    // [N][CoutP][4] = (cA, cB, cC, mean); padded channels hold zeros
+  void* dy;             // bf16 CB8 [N][CBout][Ho][Wo], written (pixels of the image only)
+  int zpad;
+};
+
 // filter-gradient partial slab (one per reduction workgroup): P[tap][16-channel input chunk][co][16] f32 followed by
 // the bias gradient [CoutP].  The 16 input channels of a chunk are the fastest axis so that the 16-lane groups of
 // the MFMA accumulator layout store 64 contiguous bytes (a [co][ci][tap] layout scattered 4-byte stores 100 B

@@ -571,11 +571,20 @@ __global__ __launch_bounds__(256, DROP ? 5 : 6) void k_gn_bwd_reduce(GnArgs a, c
 // dgamma[c] += sum_n s2[n][c], dbeta[c] += sum_n s1[n][c].  DETERMINISTIC: the 16 waves of the block take the samples
 // round-robin, park their per-(sample, channel) sums in LDS, and one thread per (channel, kind) adds them in sample order
 // (round 1 used N float atomics per channel: the training step was not reproducible from run to run).
+// One row of the table mc_conv2d_wgrad_dz reads: dzc[n][c] = (cA, cB, cC, mean) with dy = cA dz + (cB (z - mean) + cC), the
+// expressions of k_gn_bwd_apply_dz on the same f32 (m1, m2) that go to m12.
+__device__ __forceinline__ void write_dz_coef(const float* __restrict__ coef4, float* __restrict__ dzc, int n, int CP, int c,
+                                              float m1, float m2) {
+  const float4 c4 = reinterpret_cast<const float4*>(coef4)[(size_t)n * CP + c];
+  reinterpret_cast<float4*>(dzc)[(size_t)n * CP + c] = make_float4(c4.x, -c4.w * c4.w * m2, -c4.w * m1, c4.z);
+}
+
 constexpr int GNF_CHUNK = 256;          // samples per LDS round
 __global__ __launch_bounds__(1024) void k_gn_bwd_finalize(const float* __restrict__ part, int N, int blocks, int C, int CP,
                                                           int groups, int hw, const float* __restrict__ gamma,
                                                           float* __restrict__ m12, float* __restrict__ dgamma,
-                                                          float* __restrict__ dbeta) {
+                                                          float* __restrict__ dbeta, const float* __restrict__ coef4,
+                                                          float* __restrict__ dzc) {
   const int g = blockIdx.x, cpg = C / groups;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
   __shared__ float sm[GNF_CHUNK][16];                      // [sample][2 * channel-in-group + (0: s1, 1: s2)], cpg <= 8
@@ -596,6 +605,10 @@ __global__ __launch_bounds__(1024) void k_gn_bwd_finalize(const float* __restric
         if (lane == 0 && m12) {
           m12[((size_t)n * groups + g) * 2 + 0] = (float)(m1 / M);
           m12[((size_t)n * groups + g) * 2 + 1] = (float)(m2 / M);
+        }
+        if (dzc) {                                          // (lane 0's values: the ones m12 holds)
+          const float f1 = __shfl((float)(m1 / M), 0, 64), f2 = __shfl((float)(m2 / M), 0, 64);
+          if (lane < cpg) write_dz_coef(coef4, dzc, n, CP, c, f1, f2);
         }
       }
       __syncthreads();
@@ -650,6 +663,8 @@ __global__ __launch_bounds__(1024) void k_gn_bwd_finalize(const float* __restric
       if (lane == 0) {
         m12[((size_t)n * groups + g) * 2 + 0] = (float)(m1 / M);
         m12[((size_t)n * groups + g) * 2 + 1] = (float)(m2 / M);
+        if (dzc)
+          for (int c = g * cpg; c < (g + 1) * cpg; ++c) write_dz_coef(coef4, dzc, n, CP, c, (float)(m1 / M), (float)(m2 / M));
       }
     }
   }
@@ -662,10 +677,12 @@ __global__ __launch_bounds__(1024) void k_gn_bwd_finalize(const float* __restric
 // The four waves take a quarter of the slots each and are combined in a fixed order (deterministic).
 __global__ __launch_bounds__(256) void k_gn_bwd_finalize_n(const float* __restrict__ part, int blocks, int C, int CP, int groups, int hw,
                                                            const float* __restrict__ gamma, float* __restrict__ m12,
-                                                           float* __restrict__ pc) {
+                                                           float* __restrict__ pc, const float* __restrict__ coef4,
+                                                           float* __restrict__ dzc) {
   const int g = blockIdx.x, n = blockIdx.y, cpg = C / groups;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   __shared__ double sm[4][16];
+  __shared__ float mf[2];
   const int per = (blocks + 3) / 4, b0 = wave * per, cnt = max(0, min(per, blocks - b0));
   double a1, a2;
   group_channel_sums(part, (size_t)n * blocks + b0, cnt, CP, g * cpg, cpg, a1, a2);      // cpg is a power of two <= 8 (host check)
@@ -681,6 +698,11 @@ __global__ __launch_bounds__(256) void k_gn_bwd_finalize_n(const float* __restri
     double m = 0.0;
     for (int k = 0; k < cpg; ++k) m += (double)(gamma ? gamma[g * cpg + k] : 1.f) * sm[0][2 * k + threadIdx.x];
     m12[((size_t)n * groups + g) * 2 + threadIdx.x] = (float)(m / ((double)cpg * (double)hw));
+    mf[threadIdx.x] = (float)(m / ((double)cpg * (double)hw));
+  }
+  if (dzc) {                                                // (the host passes dzc only together with m12)
+    __syncthreads();
+    if ((int)threadIdx.x < cpg) write_dz_coef(coef4, dzc, n, CP, g * cpg + threadIdx.x, mf[0], mf[1]);
   }
 }
 
@@ -2154,7 +2176,7 @@ int mc_gn_act_bwd_finalize(const float* partials, int32_t n, int32_t blocks, int
                            const float* gamma, float* m12, float* dgamma, float* dbeta, void* stream) {
   if (!partials || n <= 0 || blocks <= 0 || c <= 0 || groups <= 0 || c % groups || hw <= 0) return MC_EINVAL;
   hipLaunchKernelGGL(k_gn_bwd_finalize, dim3(groups), dim3(1024), 0, (hipStream_t)stream, partials, n, blocks, c,
-                     ((c + 7) / 8) * 8, groups, hw, gamma, m12, dgamma, dbeta);
+                     ((c + 7) / 8) * 8, groups, hw, gamma, m12, dgamma, dbeta, (const float*)nullptr, (float*)nullptr);
   MC_CHECK_LAUNCH();
   return MC_OK;
 }
@@ -2165,7 +2187,30 @@ int mc_gn_act_bwd_finalize_n(const float* partials, int32_t n, int32_t blocks, i
   const int cpg = c / groups;
   if (cpg != 1 && cpg != 2 && cpg != 4 && cpg != 8) return MC_EUNSUPPORTED;
   hipLaunchKernelGGL(k_gn_bwd_finalize_n, dim3(groups, n), dim3(256), 0, (hipStream_t)stream, partials, blocks, c,
-                     ((c + 7) / 8) * 8, groups, hw, gamma, m12, chan_sums);
+                     ((c + 7) / 8) * 8, groups, hw, gamma, m12, chan_sums, (const float*)nullptr, (float*)nullptr);
+  MC_CHECK_LAUNCH();
+  return MC_OK;
+}
+
+int mc_gn_act_bwd_finalize_dz(const float* partials, int32_t n, int32_t blocks, int32_t c, int32_t groups, int32_t hw,
+                              const float* gamma, float* m12, float* dgamma, float* dbeta, const float* coef, float* dz_coef,
+                              void* stream) {
+  if (!partials || !m12 || !coef || !dz_coef || n <= 0 || blocks <= 0 || c <= 0 || groups <= 0 || c % groups || hw <= 0) return MC_EINVAL;
+  hipLaunchKernelGGL(k_gn_bwd_finalize, dim3(groups), dim3(1024), 0, (hipStream_t)stream, partials, n, blocks, c,
+                     ((c + 7) / 8) * 8, groups, hw, gamma, m12, dgamma, dbeta, coef, dz_coef);
+  MC_CHECK_LAUNCH();
+  return MC_OK;
+}
+
+int mc_gn_act_bwd_finalize_n_dz(const float* partials, int32_t n, int32_t blocks, int32_t c, int32_t groups, int32_t hw,
+                                const float* gamma, float* m12, float* chan_sums, const float* coef, float* dz_coef,
+                                void* stream) {
+  if (!partials || !chan_sums || !m12 || !coef || !dz_coef || n <= 0 || blocks <= 0 || c <= 0 || groups <= 0 || c % groups || hw <= 0)
+    return MC_EINVAL;
+  const int cpg = c / groups;
+  if (cpg != 1 && cpg != 2 && cpg != 4 && cpg != 8) return MC_EUNSUPPORTED;
+  hipLaunchKernelGGL(k_gn_bwd_finalize_n, dim3(groups, n), dim3(256), 0, (hipStream_t)stream, partials, blocks, c,
+                     ((c + 7) / 8) * 8, groups, hw, gamma, m12, chan_sums, coef, dz_coef);
   MC_CHECK_LAUNCH();
   return MC_OK;
 }

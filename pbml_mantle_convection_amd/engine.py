@@ -561,6 +561,10 @@ class Engine:
         # 8.5 packed-f16 / mixed-precision instructions per element on the loader waves, beside the next stage's MFMAs,
         # instead of the ~25 f32 instructions that made the same fusion lose in round 2.
         self.fuse_dz_rr = precision == "mixed" and os.environ.get("MANTLE_FUSE_DZ_RR", "1") != "0"
+        # "mixed" mode: the filter-gradient launch of a layer whose dz comes from its consumer's input-gradient launch forms dY
+        # from (dz, z) while it stages its tiles and stores it, instead of a stand-alone mc_gn_bwd_apply_dz pass
+        # (single-chunk, single-group layers: 10->16 and 16->16).  0 selects the apply pass (A/B).
+        self.wgrad_dz = precision == "mixed" and os.environ.get("MANTLE_WGRAD_DZ", "1") != "0"
         # GroupNorm + activation of layers with at most this many pixels run as ONE launch per direction (statistics + apply
         # forward; reduce + finalize + apply backward).  MI355X, CFG-3: 64 x 64 and 32 x 32 layers 21 -> 11 us forward and
         # 38 -> 24 us backward; 128 x 128 layers break even (25 -> 24, 49 -> 53 us: 128 blocks do not fill the chip)
@@ -732,6 +736,10 @@ class Engine:
                  part=torch.empty((N, tiles, coutp, 2), **f32),
                  bank=torch.empty(L.call("mc_packed_weight_bytes", C.byref(d), 0), dtype=torch.uint8, device=device),
                  need_dgrad=shape.dgrad)
+        # this layer's filter-gradient launch may form dY from dz itself (mc_conv2d_wgrad_dz: "mixed", one input-channel chunk,
+        # one output-channel group, sources read as they are); whether it does is settled where its dz is planned, below
+        e["wdz_ok"] = (self.wgrad_dz and self.mc_dtype == L.MC_MIX16 and node.post == L.POST_GN_ACT and node.c_out <= 16
+                       and sum((s.C + 7) // 8 for s in srcs) <= 2 and not any(s.fused for s in srcs))
         cons = self.cons[node.out]
         fusable = all(c.kind == "up" or (c.kind == "conv" and not c.learned and not c.spectral) for c in cons)
         o.fused = bool((self.fuse & 1) and node.post != L.POST_NONE and fusable and (cons or node.pool > 1)
@@ -775,6 +783,10 @@ class Engine:
                 if (pe["node"].post == L.POST_GN_ACT and pe["dz_blocks"] > 256
                         and (pe["node"].c_out // pe["node"].groups) in (1, 2, 4, 8)):
                     pe["dz_pc"] = torch.empty((N, pe["coutp"], 2), **f32)
+                if pe.get("wdz_ok"):
+                    # no apply launch: the finalize writes (cA, cB, cC, mean) per (sample, channel), the filter-gradient
+                    # launch forms dY from (dz, z) and stores it for the input-gradient launch (padded channels stay 0)
+                    pe["dz_coef"] = torch.zeros((N, pe["coutp"], 4), **f32)
         # per-layer filter-gradient partial slabs: all layers are combined by ONE batched launch at the end of backward
         e["wpart"] = torch.empty(L.call("mc_wgrad_partial_bytes", C.byref(d)), dtype=torch.uint8, device=device)
         return e
@@ -1141,24 +1153,32 @@ class Engine:
             d = e.get("desc")
             o = T[node.out]
             srcs = [T[i] for i in node.srcs]
+            wdz = False
             if node.post != L.POST_NONE and "dz" in e:
                 # dz = dA * act'(z) and its partial sums were produced by the consumer's input-gradient launch
                 assert not o.gsrcs, f"{node.name}: fused dz and separate gradient sources"
+                wdz = "dz_coef" in e                     # dY is formed by the filter-gradient launch below
                 if node.post == L.POST_GN_ACT:
                     gamma = self._param(params, node.gn_name + "weight")
+                    sfx, tab = ("_dz", (L.ptr(e["coef"]), L.ptr(e["dz_coef"]))) if wdz else ("", ())
                     if "dz_pc" in e:
                         # many slots per sample: one block per (group, sample); dgamma / dbeta join the batched launch below
-                        L.call("mc_gn_act_bwd_finalize_n", L.ptr(e["dz_part"]), N, e["dz_blocks"], node.c_out, node.groups,
-                               o.H * o.W, L.ptr(gamma), L.ptr(e["m12"]), L.ptr(e["dz_pc"]), st)
+                        L.call("mc_gn_act_bwd_finalize_n" + sfx, L.ptr(e["dz_part"]), N, e["dz_blocks"], node.c_out, node.groups,
+                               o.H * o.W, L.ptr(gamma), L.ptr(e["m12"]), L.ptr(e["dz_pc"]), *tab, st)
                         gp_jobs.append((L.ptr(e["dz_pc"]), node.c_out, L.ptr(grads[node.gn_name + "weight"]),
                                         L.ptr(grads[node.gn_name + "bias"])))
                     else:
-                        L.call("mc_gn_act_bwd_finalize", L.ptr(e["dz_part"]), N, e["dz_blocks"], node.c_out, node.groups,
+                        L.call("mc_gn_act_bwd_finalize" + sfx, L.ptr(e["dz_part"]), N, e["dz_blocks"], node.c_out, node.groups,
                                o.H * o.W, L.ptr(gamma), L.ptr(e["m12"]), L.ptr(grads[node.gn_name + "weight"]),
-                               L.ptr(grads[node.gn_name + "bias"]), st)
-                L.call("mc_gn_bwd_apply_dz", C.byref(e["dz"]), L.ptr(e["Y"]), N, node.c_out, o.H, o.W, max(node.groups, 1),
-                       L.ptr(e["coef"]) if node.post == L.POST_GN_ACT else None, L.ptr(e.get("m12")), self.mc_dtype,
-                       L.ptr(dY), st)
+                               L.ptr(grads[node.gn_name + "bias"]), *tab, st)
+                if wdz:
+                    x0, x1, _ = self._sources(srcs)
+                    L.call("mc_conv2d_wgrad_dz", C.byref(d), x0, x1, C.byref(e["dz"]), L.ptr(e["Y"]), L.ptr(e["dz_coef"]),
+                           L.ptr(dY), L.ptr(e["wpart"]), st)
+                else:
+                    L.call("mc_gn_bwd_apply_dz", C.byref(e["dz"]), L.ptr(e["Y"]), N, node.c_out, o.H, o.W, max(node.groups, 1),
+                           L.ptr(e["coef"]) if node.post == L.POST_GN_ACT else None, L.ptr(e.get("m12")), self.mc_dtype,
+                           L.ptr(dY), st)
                 del e["dz"]
             elif node.post != L.POST_NONE:
                 gs = list(o.gsrcs)
@@ -1197,8 +1217,9 @@ class Engine:
             if node.spectral:
                 self._spectral_backward(e, srcs[0], dY, params, grads, st)
                 continue
-            x0, x1, pro = self._sources(srcs)
-            L.call("mc_conv2d_wgrad_fused", C.byref(d), x0, x1, pro, L.ptr(dY), L.ptr(e["wpart"]), st)
+            if not wdz:
+                x0, x1, pro = self._sources(srcs)
+                L.call("mc_conv2d_wgrad_fused", C.byref(d), x0, x1, pro, L.ptr(dY), L.ptr(e["wpart"]), st)
             if e["need_dgrad"]:
                 dxp = e["dxp"]
                 pe = e.get("epi")
