@@ -593,6 +593,38 @@ int mc_adnet_step(const float* u, const float* v, int64_t uv_stride, const float
                   const float* raq_field, const float* raq_scalar, const float* xc, const float* yc, int32_t n, int32_t h,
                   int32_t w, float cn_max, int32_t compute_dt, float* dt_io, uint32_t* ws, float* T_next, void* stream);
 
+/* ---- ensemble rollout: b members, each with its own CFL step, clock and stopping time ("Ensemble rollout") ----
+ * Device state: T [b][h][w] f32, t [b] f64, t_end [b] f64 (+inf = never stop), steps [b] int32; member m is active iff
+ * t[m] < t_end[m].  Every entry point returns MC_EINVAL, launching nothing, for a null pointer (vel_scale alone may be
+ * NULL = 1), b <= 0 or b > 65535, h < 5 or w < 5, a uv_stride below h * w, n_steps <= 0 or a cursor outside [0, n_steps].
+ * The library allocates nothing.
+ * mc_rollout_blocks: workgroups per member of the step kernel, a function of (h, w) alone, so that a member's partial sums
+ * do not depend on b; partials holds b * blocks * 8 doubles. */
+int32_t mc_rollout_blocks(int32_t h, int32_t w);
+/* dx_min[0] = the smallest x[i][j] - x[i][j-1] of the interior (side coordinates 0 / 4 substituted): the grid spacing of
+ * mc_adnet_step's CFL step, computed once per grid instead of once per step. */
+int mc_rollout_dx_min(const float* xc, int32_t h, int32_t w, float* dx_min, void* stream);
+/* Per-member time step: uv_m = max(|s_m u|, |s_m v|) over member m's interior (ws: b x uint32 scratch),
+ * dt[m] = fminf(0.5f cn_max dx_min / uv_m, 0.5f dx2 dx2 / (dx2 + dx2)) -- mc_adnet_step's expression, the diffusive limit
+ * for a member at rest -- as an f64; flags[m] = 1.  A step that reaches the stopping time, t[m] + dt[m] >= t_end[m], is
+ * shortened to dt[m] = t_end[m] - t[m] with flags[m] = 2; an inactive member gets dt[m] = 0, flags[m] = 0. */
+int mc_rollout_dt(const float* u, const float* v, int64_t uv_stride, const float* vel_scale, const float* dx_min,
+                  const double* t, const double* t_end, int32_t b, int32_t h, int32_t w, float cn_max, uint32_t* ws, double* dt,
+                  int32_t* flags, void* stream);
+/* mc_adnet_step's stencil with (float)dt[m] per member, wall rows and side columns included; a member with flags[m] = 0 is
+ * copied.  The same launch leaves per-workgroup f64 partial sums of the six diagnostics in partials. */
+int mc_rollout_step(const float* u, const float* v, int64_t uv_stride, const float* vel_scale, const float* T_prev,
+                    const float* raq_scalar, const float* xc, const float* yc, const double* dt, const int32_t* flags, int32_t b,
+                    int32_t h, int32_t w, float* T_next, double* partials, void* stream);
+/* Reduces the partial sums in a fixed order and writes row cursor[0] of hist [n_steps][b][8] = (t after the step, dt, mean T,
+ * v_rms, Nu_bot, Nu_top, min T, max T) of T_next and of the velocity the step used; advances t[m] (set TO t_end[m] when
+ * flags[m] = 2) and steps[m] of the members that stepped, then cursor[0].  With the cursor at n_steps the row is dropped. */
+int mc_rollout_finalize(const double* partials, const double* dt, const int32_t* flags, const double* t_end, double* t,
+                        int32_t* steps, int32_t* cursor, double* hist, int32_t n_steps, int32_t b, int32_t h, int32_t w,
+                        void* stream);
+/* cursor[0] = row with a one-thread kernel on `stream`. */
+int mc_rollout_set_cursor(int32_t* cursor, int32_t row, int32_t n_steps, void* stream);
+
 /* ---- spectral layer (SpectralConv2d, pytorch_networks_convae.py:571-635) as a truncated DFT ---- */
 /* Only the modes K1 = (0, 1, 2, 3, h-4, h-3, h-2, h-1) x K2 = (0, 1, 2, 3) of rfft2 survive the layer; mode index
  * m = k1i * 4 + k2.  Twiddle tables (f32, built on the host in f64 from integer-reduced arguments):

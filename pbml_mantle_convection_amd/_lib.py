@@ -197,6 +197,12 @@ SIGNATURES = {
     "mc_ts_wall_bc": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp]),
     "mc_adnet_step": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _i32, _vp, _vp, _vp,
                                 _vp]),
+    "mc_rollout_blocks": (_i32, [_i32, _i32]),
+    "mc_rollout_dx_min": (C.c_int, [_vp, _i32, _i32, _vp, _vp]),
+    "mc_rollout_dt": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp]),
+    "mc_rollout_step": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "mc_rollout_finalize": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
+    "mc_rollout_set_cursor": (C.c_int, [_vp, _i32, _i32, _vp]),
     "mc_loss_minmax": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "mc_loss_fwd_bwd": (C.c_int, [_LD, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mc_loss_fused": (C.c_int, [_LD, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
@@ -221,7 +227,7 @@ SIGNATURES = {
 VALUE_RETURNING = {"mc_version", "mc_strerror", "mc_conv_kernel_name", "mc_packed_weight_bytes", "mc_conv_bank_read_extent", "mc_conv_tiles",
                    "mc_wgrad_partial_bytes", "mc_gn_bwd_blocks",
                    "mc_learned_validate", "mc_learned_bank_bytes", "mc_learned_wgrad_workspace_bytes", "mc_fold_blocks", "mc_loss_fused_blocks",
-                   "mc_spectral_slots", "mc_philox4x32", "mc_grad_norm_blocks", "mc_newad_noise_host"}
+                   "mc_spectral_slots", "mc_philox4x32", "mc_grad_norm_blocks", "mc_newad_noise_host", "mc_rollout_blocks"}
 
 _lib = None
 
