@@ -625,6 +625,27 @@ int mc_rollout_finalize(const double* partials, const double* dt, const int32_t*
 /* cursor[0] = row with a one-thread kernel on `stream`. */
 int mc_rollout_set_cursor(int32_t* cursor, int32_t row, int32_t n_steps, void* stream);
 
+/* ---- ensemble rollout statistics: depth profiles, their time sums, saves at fixed simulated times ----
+ * Both entry points return MC_EINVAL, launching nothing, for a null pointer (vel_scale may be NULL = 1, prof may be NULL),
+ * b <= 0 or b > 65535, h < 5 or w < 5, a uv_stride below h * w, capacity <= 0 or T_new == snaps.
+ * mc_ensemble_profiles reads the state a step STARTS from: the velocity planes u, v [b][h][w] (batch stride uv_stride,
+ * multiplied by vel_scale[m] as mc_rollout_step forms s u, s v: one f32 product) and T [b][h][w], the field that velocity was
+ * computed from; dt, flags of mc_rollout_dt, t before mc_rollout_finalize advances it.  prof [b][4][h] f64 = the mean over
+ * ALL w columns of row i of (T, (s u)^2, (s v)^2, (s v) T), squares, products and sums in f64: one wave per row, lane l adds
+ * columns l, l + 64, ... in order, then the xor tree, then / w.  Time weight of member m: 0 when flags[m] = 0, else
+ * t_avg_start[m] <= t[m] ? dt[m] : fmax(0, (t[m] + dt[m]) - t_avg_start[m]).  With a positive weight acc [b][4][h] += weight *
+ * prof (one multiply, one add), wsum[m] += weight, nacc[m] += 1; with weight 0 nothing of member m is written but prof. */
+int mc_ensemble_profiles(const float* u, const float* v, int64_t uv_stride, const float* vel_scale, const float* T,
+                         const double* dt, const int32_t* flags, const double* t, const double* t_avg_start, int32_t b,
+                         int32_t h, int32_t w, double* prof, double* acc, double* wsum, int32_t* nacc, void* stream);
+/* After mc_rollout_finalize (t is the new clock, T_new [b][h][w] the field just written).  Member m saves iff flags[m] != 0,
+ * save_every[m] > 0 and t[m] > next_save[m]; then, with count[m] < capacity, slot[m] = count[m], snap_t[m][slot] = t[m],
+ * count[m] += 1 and the plane is copied to snaps [b][capacity][h][w]; with the slots used up slot[m] = -1 and missed[m] += 1;
+ * either way next_save[m] = t[m] + save_every[m].  A member that does not save gets slot[m] = -1.  snap_t [b][capacity]. */
+int mc_ensemble_snapshot(const float* T_new, const double* t, const int32_t* flags, const double* save_every, double* next_save,
+                         int32_t* count, int32_t* missed, int32_t* slot, int32_t capacity, int32_t b, int32_t h, int32_t w,
+                         float* snaps, double* snap_t, void* stream);
+
 /* ---- spectral layer (SpectralConv2d, pytorch_networks_convae.py:571-635) as a truncated DFT ---- */
 /* Only the modes K1 = (0, 1, 2, 3, h-4, h-3, h-2, h-1) x K2 = (0, 1, 2, 3) of rfft2 survive the layer; mode index
  * m = k1i * 4 + k2.  Twiddle tables (f32, built on the host in f64 from integer-reduced arguments):

@@ -7,7 +7,8 @@ synchronisation inside the loop; six diagnostics per member and step are accumul
 (pytorch_networks_convae.py) stay the batch-1 restatement of the reference's wrapper; this module is beside them.
 
     python -m pbml_mantle_convection_amd.rollout --params params.csv --steps 100 --out DIR --synthetic 8 128 506 \
-        -l 5 -f 16 -r 6 -k 5 -p zeros [--weights sd.pt] [--t_end X] [--snapshot_every K] [--precision bf16]
+        -l 5 -f 16 -r 6 -k 5 -p zeros [--weights sd.pt] [--t_end X] [--snapshot_every K] [--precision bf16] \
+        [--profiles 1 [--t_avg_start X]] [--save_every DT --save_capacity S]
 """
 import argparse
 import json
@@ -20,6 +21,7 @@ from . import _lib as L
 from .datasetio import normalise_parameters
 
 HIST_NAMES = ("t", "dt", "T_mean", "v_rms", "Nu_bot", "Nu_top", "T_min", "T_max")
+PROFILE_NAMES = ("T", "u2", "v2", "vT")           # rows of a depth profile: means over a row of T, (s u)^2, (s v)^2, (s v) T
 HIST_CHUNK = 256          # rows of the device-side history buffer the captured step writes into
 
 
@@ -34,6 +36,21 @@ def broadcast_t_end(t_end, B):
         return t.expand(B).clone()
     if t.numel() != B:
         raise ValueError(f"t_end must be None, a number or hold one value per member ({B}), got {t.numel()} values")
+    return t.clone()
+
+
+def broadcast_member_value(value, B, name, default=0.0):
+    """None -> `default` for every member, a number -> every member, [B] -> per member; f64 [B] on the host.  Negative and
+    NaN values are refused (t_avg_start, save_every)."""
+    if value is None:
+        return torch.full((B,), float(default), dtype=torch.float64)
+    t = torch.as_tensor(value, dtype=torch.float64).detach().cpu().reshape(-1)
+    if bool(torch.isnan(t).any()) or bool((t < 0).any()):
+        raise ValueError(f"{name} must be neither negative nor NaN")
+    if t.numel() == 1:
+        return t.expand(B).clone()
+    if t.numel() != B:
+        raise ValueError(f"{name} must be None, a number or hold one value per member ({B}), got {t.numel()} values")
     return t.clone()
 
 
@@ -98,14 +115,23 @@ class EnsembleRollout:
     (its T is copied, its dt is 0).
 
     `stokes(inp [B,7,H,W]) -> (u, v, p)` is a NewFluidNet (or a module around one); it belongs to this rollout: the captured
-    step replays the engine's buffers of this (B, H, W), and a forward of the same module at another shape re-plans them."""
+    step replays the engine's buffers of this (B, H, W), and a forward of the same module at another shape re-plans them.
 
-    def __init__(self, stokes, device, CN_max=0.1, precision=None, use_graph=True):
+    `profiles=True` adds mc_ensemble_profiles to the step: the horizontally averaged T, (s u)^2, (s v)^2 and (s v) T of the
+    state every step starts from, and their time-weighted sums from t_avg_start[b] on.  `save_capacity=S > 0` adds
+    mc_ensemble_snapshot: up to S fields per member and run, saved when the member's own clock passes its next saving time
+    (save_every[b] apart).  With both off the step issues the same launches as before and nothing else changes."""
+
+    def __init__(self, stokes, device, CN_max=0.1, precision=None, use_graph=True, profiles=False, save_capacity=0):
         self.stokes, self.CN_max, self.use_graph = stokes, float(CN_max), bool(use_graph)
         self.device = device if isinstance(device, torch.device) else torch.device(device)
+        if isinstance(save_capacity, bool) or int(save_capacity) != save_capacity or int(save_capacity) < 0:
+            raise ValueError(f"save_capacity must be a non-negative integer, got {save_capacity!r}")
+        self.profiles, self.save_capacity = bool(profiles), int(save_capacity)
         if precision is not None:
             stokes.set_precision(precision)
         self._s = None          # member state
+        self._x = None          # statistics of the members (profiles / save_capacity): the captured step reads them by address
         self._g = None          # grid, parameters, work buffers and the captured step of one (B, H, W)
 
     # ---- member state ---------------------------------------------------------------------------------------------
@@ -117,13 +143,28 @@ class EnsembleRollout:
                            t_end=torch.full((B,), float("inf"), dtype=torch.float64, device=dev),
                            steps=torch.zeros(B, dtype=torch.int32, device=dev))
             self._g = None      # the captured step reads the state by address
+            if self.profiles or self.save_capacity:
+                f64, i32, S = dict(dtype=torch.float64, device=dev), dict(dtype=torch.int32, device=dev), self.save_capacity
+                self._x = dict(t_avg_start=torch.zeros(B, **f64), acc=torch.zeros((B, 4, H), **f64), last=torch.zeros((B, 4, H), **f64),
+                               weight=torch.zeros(B, **f64), count=torch.zeros(B, **i32), save_every=torch.zeros(B, **f64),
+                               next_save=torch.zeros(B, **f64), saved=torch.zeros(B, **i32), missed=torch.zeros(B, **i32),
+                               slot=torch.full((B,), -1, **i32))
+                if S:
+                    self._x.update(snaps=torch.zeros((B, S, H, W), dtype=torch.float32, device=dev),
+                                   snap_t=torch.full((B, S), float("nan"), **f64))
         return self._s
 
+    STATS_KEYS = ("acc", "weight", "count", "next_save")
+
     def state(self):
-        """Copies of T, t, t_end, steps: enough to stop a study and continue it (load_state) on the same grid and parameters."""
+        """Copies of T, t, t_end, steps: enough to stop a study and continue it (load_state) on the same grid and parameters.
+        With profiles or timed saves on, also "stats": the time sums acc [B,4,H], their weight [B] and count [B], next_save [B]."""
         if self._s is None:
             raise RuntimeError("no state: call reset() or load_state() first")
-        return {k: v.clone() for k, v in self._s.items()}
+        st = {k: v.clone() for k, v in self._s.items()}
+        if self._x is not None:
+            st["stats"] = {k: self._x[k].clone() for k in self.STATS_KEYS}
+        return st
 
     def load_state(self, state):
         T = torch.as_tensor(state["T"])
@@ -140,19 +181,37 @@ class EnsembleRollout:
         s["t"].copy_(torch.as_tensor(state["t"]).reshape(B).to(torch.float64))
         s["t_end"].copy_(torch.as_tensor(state["t_end"]).reshape(B).to(torch.float64))
         s["steps"].copy_(torch.as_tensor(state["steps"]).reshape(B).to(torch.int32))
+        stats = state.get("stats")
+        if stats is not None:
+            if self._x is None:
+                raise ValueError("state['stats'] needs a rollout built with profiles=True or save_capacity > 0")
+            for k in self.STATS_KEYS:
+                v = torch.as_tensor(stats[k])
+                if v.numel() != self._x[k].numel():
+                    raise ValueError(f"state['stats'][{k!r}] must hold {tuple(self._x[k].shape)}")
+                self._x[k].copy_(v.reshape(self._x[k].shape).to(self._x[k].dtype))
         return self
 
     # ---- grid and parameters --------------------------------------------------------------------------------------
     @torch.no_grad()
-    def reset(self, T0, xc, yc, ycc, raq, fkt, fkp, nd, t_end=None):
+    def reset(self, T0, xc, yc, ycc, raq, fkt, fkp, nd, t_end=None, t_avg_start=None, save_every=None):
         """T0 [B,1,H,W]; xc, yc, ycc [H,W] (ycc: the depth coordinate of the viscosity law, TS's `ycc`); raq, fkt, fkp [B];
-        nd [B,3] their normalised values (normalise_params); t_end None | number | [B].  Clocks and step counts restart at 0."""
+        nd [B,3] their normalised values (normalise_params); t_end None | number | [B].  Clocks and step counts restart at 0.
+        t_avg_start None (= 0) | number | [B]: the time from which the profiles are averaged (needs profiles=True);
+        save_every None (= never) | number | [B]: the simulated time between two timed saves (needs save_capacity > 0).  The
+        time sums and the save counters restart at 0 and the first saving time is 0, so a saving member's first step is saved."""
         T0 = torch.as_tensor(T0)
         if T0.dim() != 4 or T0.shape[1] != 1:
             raise ValueError(f"T0 must be [B,1,H,W], got {tuple(T0.shape)}")
         B, _, H, W = T0.shape
         if H < 5 or W < 5:
             raise ValueError("the grid must be at least 5 x 5")
+        if t_avg_start is not None and not self.profiles:
+            raise ValueError("t_avg_start needs EnsembleRollout(..., profiles=True)")
+        if save_every is not None and not self.save_capacity:
+            raise ValueError("save_every needs EnsembleRollout(..., save_capacity=S) with S > 0")
+        tas = broadcast_member_value(t_avg_start, B, "t_avg_start")
+        sev = broadcast_member_value(save_every, B, "save_every")           # 0 = never
         dev = self.device
         f = dict(dtype=torch.float32, device=dev)
         te = broadcast_t_end(t_end, B)
@@ -167,6 +226,11 @@ class EnsembleRollout:
         s["t"].zero_()
         s["steps"].zero_()
         s["t_end"].copy_(te)
+        x = self._x
+        if x is not None:
+            x["t_avg_start"].copy_(tas); x["save_every"].copy_(sev)
+            for k in ("acc", "weight", "count", "next_save", "saved", "missed"):
+                x[k].zero_()
         g = self._g
         if g is None:
             nblk = L.call("mc_rollout_blocks", H, W)
@@ -205,10 +269,19 @@ class EnsembleRollout:
         uvs = int(uu.stride(0))
         L.call("mc_rollout_dt", L.ptr(uu), L.ptr(vv), uvs, L.ptr(g["scaler"]), L.ptr(g["dx_min"]), L.ptr(s["t"]),
                L.ptr(s["t_end"]), B, H, W, self.CN_max, L.ptr(g["ws"]), L.ptr(g["dt"]), L.ptr(g["flags"]), st)
+        x = self._x
+        if self.profiles:                                       # the state this step starts from, before t and T advance
+            L.call("mc_ensemble_profiles", L.ptr(uu), L.ptr(vv), uvs, L.ptr(g["scaler"]), L.ptr(s["T"]), L.ptr(g["dt"]),
+                   L.ptr(g["flags"]), L.ptr(s["t"]), L.ptr(x["t_avg_start"]), B, H, W, L.ptr(x["last"]), L.ptr(x["acc"]),
+                   L.ptr(x["weight"]), L.ptr(x["count"]), st)
         L.call("mc_rollout_step", L.ptr(uu), L.ptr(vv), uvs, L.ptr(g["scaler"]), L.ptr(s["T"]), L.ptr(g["raq"]),
                L.ptr(g["xc"]), L.ptr(g["yc"]), L.ptr(g["dt"]), L.ptr(g["flags"]), B, H, W, L.ptr(g["Tn"]), L.ptr(g["part"]), st)
         L.call("mc_rollout_finalize", L.ptr(g["part"]), L.ptr(g["dt"]), L.ptr(g["flags"]), L.ptr(s["t_end"]), L.ptr(s["t"]),
                L.ptr(s["steps"]), L.ptr(g["cursor"]), L.ptr(g["hist"]), HIST_CHUNK, B, H, W, st)
+        if self.save_capacity:                                  # the new clock and the field just written
+            L.call("mc_ensemble_snapshot", L.ptr(g["Tn"]), L.ptr(s["t"]), L.ptr(g["flags"]), L.ptr(x["save_every"]),
+                   L.ptr(x["next_save"]), L.ptr(x["saved"]), L.ptr(x["missed"]), L.ptr(x["slot"]), self.save_capacity, B, H, W,
+                   L.ptr(x["snaps"]), L.ptr(x["snap_t"]), st)
         s["T"].view(B, H, W).copy_(g["Tn"])
         g["out"] = (uu, vv, pp)
 
@@ -218,6 +291,7 @@ class EnsembleRollout:
     def _capture(self):
         s, g = self._s, self._g
         keep = {k: s[k].clone() for k in ("T", "t", "steps")}
+        xkeep = {k: v.clone() for k, v in self._x.items()} if self._x is not None else {}
         self._set_cursor(0)
         side = torch.cuda.Stream(device=self.device)
         side.wait_stream(torch.cuda.current_stream())
@@ -227,6 +301,8 @@ class EnsembleRollout:
         torch.cuda.synchronize(self.device)
         for k, v in keep.items():                               # the warm-up advanced the members: put them back
             s[k].copy_(v)
+        for k, v in xkeep.items():                              # ... and their statistics
+            self._x[k].copy_(v)
         g["graph"] = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g["graph"]):
             self._one_step()
@@ -236,7 +312,11 @@ class EnsembleRollout:
         """Advance n_steps (members past their t_end stay frozen); continues where the last run ended.  Returns a dict: T
         [B,1,H,W], t [B] f64, steps [B] int32, hist [n_steps,B,8] f64 with the columns `names`, snapshots [S,B,H,W] (the
         states after every snapshot_every-th step of this run) or None, and u, v, p of the last step, un-scaled as TS
-        returns them.  Nothing here waits for the device."""
+        returns them; `profiles` (None, or names, acc [B,4,H], weight [B], count [B], mean = acc / weight where weight > 0
+        else 0, last [B,4,H]: the profile of the state the last step started from) and `timed` (None, or T [B,S,H,W],
+        t [B,S], count [B], missed [B]: the fields saved during THIS run at each member's saving times, slots from count[b]
+        on are stale and their t is NaN; the next saving time carries over to the next run).  Nothing here waits for the
+        device."""
         if self._g is None or self._s is None:
             raise RuntimeError("call reset() first (load_state() alone carries no grid and no parameters)")
         n_steps, every = int(n_steps), int(snapshot_every)
@@ -249,6 +329,9 @@ class EnsembleRollout:
         with torch.cuda.device(dev):
             if self.use_graph and g["graph"] is None:
                 self._capture()
+            x = self._x
+            if self.save_capacity:                              # the timed snapshots returned belong to this run
+                x["saved"].zero_(); x["missed"].zero_(); x["snap_t"].fill_(float("nan"))
             hist = torch.empty((n_steps, B, 8), dtype=torch.float64, device=dev)
             snaps = torch.empty((n_steps // every, B, H, W), dtype=torch.float32, device=dev) if every else None
             done = 0
@@ -267,9 +350,16 @@ class EnsembleRollout:
                 done += chunk
             u, v, p = g["out"]
             sv = g["scaler"].view(B, 1, 1, 1)
+            prof = timed = None
+            if self.profiles:
+                acc, wt = x["acc"].clone(), x["weight"].clone()
+                mean = torch.where(wt.view(B, 1, 1) > 0, acc / wt.view(B, 1, 1), torch.zeros_like(acc))
+                prof = dict(names=PROFILE_NAMES, acc=acc, weight=wt, count=x["count"].clone(), mean=mean, last=x["last"].clone())
+            if self.save_capacity:
+                timed = dict(T=x["snaps"].clone(), t=x["snap_t"].clone(), count=x["saved"].clone(), missed=x["missed"].clone())
             return dict(T=s["T"].clone(), t=s["t"].clone(), steps=s["steps"].clone(), hist=hist, names=HIST_NAMES,
                         snapshots=snaps, u=u.unsqueeze(1) * sv, v=v.unsqueeze(1) * sv,
-                        p=p.reshape(B, 1, H, W) if p is not None else None)
+                        p=p.reshape(B, 1, H, W) if p is not None else None, profiles=prof, timed=timed)
 
 
 # --------------------------------------------------------------------------------------------------
@@ -289,6 +379,10 @@ def build_arg_parser():
     p.add_argument("--steps", type=int, required=True)
     p.add_argument("--t_end", type=float, default=None)
     p.add_argument("--snapshot_every", type=int, default=0)
+    p.add_argument("--profiles", type=int, default=0, help="1: depth profiles and their time averages -> profiles.npz")
+    p.add_argument("--t_avg_start", type=float, default=None, help="simulated time from which the profiles are averaged")
+    p.add_argument("--save_every", type=float, default=None, help="simulated time between two saved fields of a member")
+    p.add_argument("--save_capacity", type=int, default=0, help="saved fields per member -> timed_snapshots.npz")
     p.add_argument("--out", type=str, required=True)
     p.add_argument("--synthetic", type=int, nargs=3, metavar=("B", "H", "W"), default=None,
                    help="seeded synthetic grid and initial fields instead of --init")
@@ -334,9 +428,10 @@ def main(argv=None):
         raise SystemExit("give --synthetic B H W or --init FILE")
     dev = torch.device(a.device)
     L.load()
-    ro = EnsembleRollout(build_stokes(a, dev), dev, CN_max=a.CN_max, precision=a.precision, use_graph=bool(a.graph))
+    ro = EnsembleRollout(build_stokes(a, dev), dev, CN_max=a.CN_max, precision=a.precision, use_graph=bool(a.graph),
+                         profiles=bool(a.profiles), save_capacity=a.save_capacity)
     ro.reset(torch.from_numpy(T0), torch.from_numpy(xc), torch.from_numpy(yc), torch.from_numpy(ycc), paras[:, 0], paras[:, 1],
-             paras[:, 2], normalise_params(paras), t_end=a.t_end)
+             paras[:, 2], normalise_params(paras), t_end=a.t_end, t_avg_start=a.t_avg_start, save_every=a.save_every)
     out = ro.run(a.steps, snapshot_every=a.snapshot_every)
     os.makedirs(a.out, exist_ok=True)
     hist = out["hist"].cpu().numpy()
@@ -349,6 +444,14 @@ def main(argv=None):
                    weights=a.weights or f"random (seed {a.seed})", t=out["t"].cpu().tolist(),
                    member_steps=out["steps"].cpu().tolist(), T_mean=hist[-1, :, 2].tolist(), v_rms=hist[-1, :, 3].tolist(),
                    snapshots=int(snaps.shape[0]), finite=bool(np.isfinite(final_T).all()))
+    if out["profiles"] is not None:
+        pr = {k: (list(v) if k == "names" else v.cpu().numpy()) for k, v in out["profiles"].items()}
+        np.savez(os.path.join(a.out, "profiles.npz"), **pr)
+        summary["profiles"] = dict(names=pr["names"], weight=pr["weight"].tolist(), count=pr["count"].tolist())
+    if out["timed"] is not None:
+        tm = {k: v.cpu().numpy() for k, v in out["timed"].items()}
+        np.savez(os.path.join(a.out, "timed_snapshots.npz"), **tm)
+        summary["timed"] = dict(count=tm["count"].tolist(), missed=tm["missed"].tolist())
     line = json.dumps(summary)
     with open(os.path.join(a.out, "summary.json"), "w") as fh:
         fh.write(line + "\n")
