@@ -646,6 +646,40 @@ int mc_ensemble_snapshot(const float* T_new, const double* t, const int32_t* fla
                          int32_t* count, int32_t* missed, int32_t* slot, int32_t capacity, int32_t b, int32_t h, int32_t w,
                          float* snaps, double* snap_t, void* stream);
 
+/* ---- series scoring: a trained Stokes net against the snapshots of a simulation ("Series scoring") ----
+ * Store (f32, device): T, u, v [n_snap][h][w] with snapshot stride store_stride (un-scaled, as the files hold them), sim [n_snap]
+ * int32 (the snapshot's simulation), prev [n_snap] int32 (its baseline snapshot; outside [0, n_snap) = none), paras [n_sims][3] =
+ * (RaQ, FKT, FKP), paras_nd [n_sims][3], inv_scale [n_sims] = 1 / velocity scale.  Work list idx [n_items] int32 and a device
+ * cursor (int32): slot k of a step of b slots holds item j = min(cursor + k, n_items - 1) and snapshot s = idx[j]; only slots
+ * with cursor + k < n_items write results.  idx[j] and sim[s] are clamped into their ranges before they address anything.
+ * Every entry point returns MC_EINVAL, launching nothing, for a null pointer, b <= 0 or b > 65535, h < 3 or w < 3,
+ * n_items <= 0, n_snap <= 0, n_sims <= 0, a stride below h * w or a cursor row outside [0, n_items].  The library allocates
+ * nothing.
+ * mc_series_build_input: out [b][7][h][w], out[k] = mc_ts_build_input's seven channels for T[s] with paras[sim[s]] and
+ * paras_nd[sim[s]] (the same f32 expressions: bit-identical to mc_ts_build_input on the gathered arrays); the store is read in
+ * place. */
+int mc_series_build_input(const float* T, int64_t store_stride, const int32_t* sim, const float* xc, const float* yc,
+                          const float* ycc, const float* paras, const float* paras_nd, const int32_t* idx, const int32_t* cursor,
+                          int32_t n_items, int32_t n_snap, int32_t n_sims, int32_t b, int32_t h, int32_t w, float* out,
+                          void* stream);
+/* Row pass.  u_hat, v_hat [b][h][w] with batch stride uv_stride: the network's (scaled) velocities, read in place.  In the scaled
+ * space ut = u[s][i][j] * inv_scale[sim[s]] (ONE f32 product), likewise vt, and ub, vb from snapshot prev[s]; every difference,
+ * absolute value and sum is f64.  One wave per row (k, i): lane l takes columns l, l + 64, ... in ascending order, then the xor
+ * tree.  rows [b][10][h] f64 = sum|ut-u_hat|, sum|vt-v_hat|, sum|ut-ub|, sum|vt-vb| (NaN without a baseline), max|ut|, max|vt|,
+ * max|ut-u_hat|, max|vt-v_hat|, and over the interior columns of interior rows sum|div(u_hat,v_hat)|, sum|div(ut,vt)| with
+ * div(a,b)[i][j] = 0.5 (a[i][j+1] - a[i][j-1]) + 0.5 (b[i+1][j] - b[i-1][j]) (0 on the first and last row). */
+int mc_series_score(const float* u_hat, const float* v_hat, int64_t uv_stride, const float* u, const float* v, int64_t store_stride,
+                    const int32_t* sim, const int32_t* prev, const float* inv_scale, const int32_t* idx, const int32_t* cursor,
+                    int32_t n_items, int32_t n_snap, int32_t n_sims, int32_t b, int32_t h, int32_t w, double* rows, void* stream);
+/* Adds (takes the maximum of) the row results over i ascending and writes table [n_items][10] f64, row j = (mae_u, mae_v, base_u,
+ * base_v: sums / (h w); max_u, max_v, maxerr_u, maxerr_v; mass_pred, mass_true: sums / ((h-2)(w-2))), and profile
+ * [n_items][2][h] = the row means (/ w) of |ut-u_hat| and |vt-v_hat|; one wave per slot.  Slots past the end of the list write
+ * nothing.  Then, in a one-thread launch of its own behind it, cursor[0] = min(cursor[0] + b, n_items). */
+int mc_series_score_finalize(const double* rows, const int32_t* idx, int32_t* cursor, int32_t n_items, int32_t n_snap, int32_t b,
+                             int32_t h, int32_t w, double* table, double* profile, void* stream);
+/* cursor[0] = row with a one-thread kernel on `stream`. */
+int mc_series_set_cursor(int32_t* cursor, int32_t row, int32_t n_items, void* stream);
+
 /* ---- spectral layer (SpectralConv2d, pytorch_networks_convae.py:571-635) as a truncated DFT ---- */
 /* Only the modes K1 = (0, 1, 2, 3, h-4, h-3, h-2, h-1) x K2 = (0, 1, 2, 3) of rfft2 survive the layer; mode index
  * m = k1i * 4 + k2.  Twiddle tables (f32, built on the host in f64 from integer-reduced arguments):

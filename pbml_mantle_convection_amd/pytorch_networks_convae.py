@@ -573,15 +573,17 @@ class TS(nn.Module):
     """Evaluation wrapper for time stepping (reference :266-476), 'newfluidnet' branch with an advection net: ts times
     { input builder -> Stokes net -> un-scale u, v -> ADNet step -> boundary rows / columns }, every stage a HIP kernel on
     HBM-resident planes (no host round trip inside the loop).  Same constructor and forward signature as the reference;
-    returns (x dict, dts dict, u, v, p, V)."""
+    returns (x dict, dts dict, u, v, p, V).  With ad=None and ts=1 (the reference's ML_STOKES mode) the input is built and the
+    Stokes net evaluated once: x == {0: T_prev}, dts == {}, and u, v, p, V are what the advection branch returns."""
 
     def __init__(self, stokes, ad, device, ts=8, advection_scheme=2, scale=True, p_pred=True, net="fluidnet", use_graph=False):
         super().__init__()
         self.use_graph, self._g = bool(use_graph), None        # use_graph: one rollout step captured as a HIP graph and replayed
         if net not in ("newfluidnet", "unet"):
             raise NotImplementedError("TS on the HIP path covers net='newfluidnet' (the deployed configuration) and 'unet'")
-        if ad is None and net == "newfluidnet":
-            raise NotImplementedError("TS needs the advection net (ADNet)")
+        if ad is None and net == "newfluidnet" and ts != 1:
+            raise ValueError("TS without an advection net evaluates the Stokes net once (the reference's ML_STOKES mode): ts must be "
+                             f"1, got {ts} (the reference fails there with a KeyError on x[1], which no advection step has written)")
         self.stokes, self.ad, self.ts, self.device = stokes, ad, ts, device
         self.advection_scheme, self.scale, self.p_pred, self.net = advection_scheme, scale, p_pred, net
 
@@ -620,8 +622,9 @@ class TS(nn.Module):
             uu, vv, pp = self.stokes(st["inp"])
             uu = uu.reshape(B, H, W).contiguous()
             vv = vv.reshape(B, H, W).contiguous()
-            self.ad.step(uu, vv, st["T"].view(B, H, W), st["xc"], st["yc"], raq_scalar=st["raq"], vel_scale=st["scaler"],
-                         out=st["Tn"], dt_out=st["dt"])
+            if self.ad is not None:
+                self.ad.step(uu, vv, st["T"].view(B, H, W), st["xc"], st["yc"], raq_scalar=st["raq"], vel_scale=st["scaler"],
+                             out=st["Tn"], dt_out=st["dt"])
             st["out"] = (uu, vv, pp)
 
         u = v = p = None
@@ -642,8 +645,9 @@ class TS(nn.Module):
             else:
                 one_step()
             u, v, p = st["out"]
-            x[i] = st["Tn"].clone().view(B, 1, H, W)
-            dts[i] = st["dt"].clone()
+            if self.ad is not None:                                 # (without an advection net: x == {0: T_prev}, dts == {})
+                x[i] = st["Tn"].clone().view(B, 1, H, W)
+                dts[i] = st["dt"].clone()
         V = torch.clip(torch.exp(-torch.log(paras[:, 1]).view(B, 1, 1, 1) * x[self.ts - 1]
                                  + torch.log(paras[:, 2]).view(B, 1, 1, 1) * (1.0 - yccp)), 1e-8, 1.0) if self.ts >= 1 else None
         sv = scaler.view(B, 1, 1, 1)
