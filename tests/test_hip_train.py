@@ -117,6 +117,12 @@ def test_momentum_residual_matches_oracle(H, W):
     (37, 64, False, 1e-6, True, True, "mass"),        # no pressure channel, scaled + derivative terms, exact tile width
     (16, 200, True, 0.0, True, False, "mae"),         # no momentum term
     (5, 9, True, 1e-6, False, True, "mass"),          # the minimum size: every pixel within two of a wall
+    # the seam shapes of tests/loss_cases.py
+    (5, 5, True, 1e-6, True, True, "mass"),           # the minimum in both directions
+    (9, 66, True, 1e-6, False, False, "mass"),        # both halo columns across a seam; one row past the 8-row tiles
+    (17, 65, False, 1e-6, True, True, "mae"),         # one row past the 16-row tile; one column past a seam
+    (33, 129, True, 1e-6, True, True, "mass"),        # one row past the 32-row tile; two column seams
+    (34, 64, True, 1e-6, False, True, "mae"),         # exact tile width
 ])
 def test_one_launch_loss_equals_the_three_kernels(monkeypatch, H, W, p_pred, lam, ls, ld, loss_type):
     """mc_loss_fused (plane form and the form that reads the last convolution's CB8 output) against mc_loss_fwd_bwd +
