@@ -164,7 +164,13 @@ int mc_conv2d(const mc_conv_desc* d, const void* x0, const void* x1, const void*
 int mc_conv2d_fused(const mc_conv_desc* d, const void* x0, const void* x1, const mc_conv_prologue* pro,
                     const void* packed_w, const float* bias, void* y0, void* y1, float* stat_partials,
                     const mc_conv_epilogue* epi, void* stream);
-/* Filter/bias gradient.  partials: workspace of mc_wgrad_partial_bytes(d); the second call
+/* Name of the instantiation mc_conv2d_fused launches for (d, pro, epi): the family name of mc_conv_kernel_name with, inside the
+ * brackets, ",norm" (prologue) or ",dz" (epilogue), ",act" where the row-reuse kernel takes its generic-activation build (not
+ * the GELU-only one), ",h16" when the launch reads f16, ",dzm" for the row-reuse epilogue on the MFMA waves.  Host only:
+ * launches nothing and needs no device; pro / epi are validated as by the launch ("unsupported" where it would fail; their
+ * pointers are not dereferenced).  Both NULL, or a prologue with nothing to do: the name mc_conv_kernel_name returns. */
+const char* mc_conv_fused_kernel_name(const mc_conv_desc* d, const mc_conv_prologue* pro, const mc_conv_epilogue* epi);
+/* Filter/bias gradient. partials: workspace of mc_wgrad_partial_bytes(d); the second call
  * reduces it deterministically, folds mirrored filters back onto the unique bank
  * (dW_unique[i] += flip_x(dW_full[U+i])) and ACCUMULATES into dw_unique / dbias. */
 size_t mc_wgrad_partial_bytes(const mc_conv_desc* d);

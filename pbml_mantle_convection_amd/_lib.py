@@ -111,6 +111,7 @@ SIGNATURES = {
     "mc_pack_weights": (C.c_int, [_CD, _vp, _i32, _vp, _vp]),
     "mc_conv_tiles": (_i32, [_CD]),
     "mc_conv_kernel_name": (C.c_char_p, [_CD]),
+    "mc_conv_fused_kernel_name": (C.c_char_p, [_CD, _CP, _CE]),
     "mc_conv2d": (C.c_int, [_CD, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mc_conv2d_fused": (C.c_int, [_CD, _vp, _vp, _CP, _vp, _vp, _vp, _vp, _vp, _CE, _vp]),
     "mc_conv2d_wgrad_fused": (C.c_int, [_CD, _vp, _vp, _CP, _vp, _vp, _vp]),
@@ -230,7 +231,7 @@ SIGNATURES = {
 }
 
 # entry points whose return value is a quantity, not a status code
-VALUE_RETURNING = {"mc_version", "mc_strerror", "mc_conv_kernel_name", "mc_packed_weight_bytes", "mc_conv_bank_read_extent", "mc_conv_tiles",
+VALUE_RETURNING = {"mc_version", "mc_strerror", "mc_conv_kernel_name", "mc_conv_fused_kernel_name", "mc_packed_weight_bytes", "mc_conv_bank_read_extent", "mc_conv_tiles",
                    "mc_wgrad_partial_bytes", "mc_gn_bwd_blocks",
                    "mc_learned_validate", "mc_learned_bank_bytes", "mc_learned_wgrad_workspace_bytes", "mc_fold_blocks", "mc_loss_fused_blocks",
                    "mc_spectral_slots", "mc_philox4x32", "mc_grad_norm_blocks", "mc_newad_noise_host", "mc_rollout_blocks"}

@@ -1,4 +1,7 @@
 // C-ABI dispatch for the convolution entry points + filter-bank packing + filter-gradient combine.
+#include <mutex>
+#include <set>
+#include <string>
 #include "conv_rr.h"
 
 int mc_conv2d_f32(const ConvGeom& g, const void* x0, const void* x1, const void* bank, const float* bias, void* y0,
@@ -237,15 +240,13 @@ static int fill_prologue(const mc_conv_prologue* pro, ConvFuse& fz, int& rc) {
   return (pro->coef0 || pro->coef1 || pro->act0 != MC_ACT_NONE || pro->act1 != MC_ACT_NONE) ? 1 : 0;
 }
 
-int mc_conv2d_fused(const mc_conv_desc* d, const void* x0, const void* x1, const mc_conv_prologue* pro,
-                    const void* packed_w, const float* bias, void* y0, void* y1, float* stat_partials,
-                    const mc_conv_epilogue* epi, void* stream) {
-  ConvGeom g;
-  int rc = geom_for(d, g);
-  if (rc) return rc;
-  if (!x0 || !packed_w || !y0 || (g.Cin1 > 0 && !x1) || (g.split8 > 0 && !y1)) return MC_EINVAL;
-  ConvFuse fz = conv_fuse_none();
-  int fuse = fill_prologue(pro, fz, rc);
+// What a launch of d with (pro, epi) fuses: fills fz and fuse (0 none, 1 prologue, 2 epilogue), or returns the launch's error.
+// mc_conv2d_fused and mc_conv_fused_kernel_name both come through here.
+static int fuse_for(const mc_conv_desc* d, const ConvGeom& g, const mc_conv_prologue* pro, const mc_conv_epilogue* epi,
+                    const float* stat_partials, ConvFuse& fz, int& fuse) {
+  int rc;
+  fz = conv_fuse_none();
+  fuse = fill_prologue(pro, fz, rc);
   if (rc) return rc;
   if (epi) {
     // input-gradient launch on the padded domain of a (hs x ws) tensor with a single, unsplit output
@@ -262,6 +263,42 @@ int mc_conv2d_fused(const mc_conv_desc* d, const void* x0, const void* x1, const
     fz.estride = epi->part_stride;
     fuse = 2;
   }
+  return MC_OK;
+}
+
+const char* mc_conv_fused_kernel_name(const mc_conv_desc* d, const mc_conv_prologue* pro, const mc_conv_epilogue* epi) {
+  ConvGeom g;
+  ConvFuse fz;
+  int fuse;
+  if (geom_for(d, g) || fuse_for(d, g, pro, epi, nullptr, fz, fuse)) return "unsupported";
+  if (fuse == 0) return mc_conv_kernel_name(d);
+  const bool rr = rr_desc(d), is16 = mc_is16(g.dtype);
+  std::string s = rr ? mc_rr_kernel_name(g, fuse) : mc_conv_kernel_name(d);
+  s.pop_back();                                             // the closing '>': the suffixes go inside
+  const char* what = fuse == 1 ? ",norm" : ",dz";
+  if (s.find(what) == std::string::npos) s += what;         // (mc_rr_kernel_name writes them itself, but not beside f32out)
+  if (rr && !rr_fuse_gelu(fz, fuse)) s += ",act";           // the generic-activation build
+  if (is16 && conv_fuse_h16(g, fz, fuse)) s += ",h16";
+  if (rr && rr_fuse_dzm(g, fz, fuse)) s += ",dzm";
+  s += ">";
+  // static storage like every other name: each distinct name is kept once
+  static std::mutex mu;
+  static std::set<std::string> names;
+  std::lock_guard<std::mutex> lock(mu);
+  return names.insert(s).first->c_str();
+}
+
+int mc_conv2d_fused(const mc_conv_desc* d, const void* x0, const void* x1, const mc_conv_prologue* pro,
+                    const void* packed_w, const float* bias, void* y0, void* y1, float* stat_partials,
+                    const mc_conv_epilogue* epi, void* stream) {
+  ConvGeom g;
+  int rc = geom_for(d, g);
+  if (rc) return rc;
+  if (!x0 || !packed_w || !y0 || (g.Cin1 > 0 && !x1) || (g.split8 > 0 && !y1)) return MC_EINVAL;
+  ConvFuse fz;
+  int fuse;
+  rc = fuse_for(d, g, pro, epi, stat_partials, fz, fuse);
+  if (rc) return rc;
   if (rr_desc(d)) return mc_conv2d_rr(g, x0, x1, packed_w, bias, y0, y1, stat_partials, fz, fuse, (hipStream_t)stream);
   if (mc_is16(g.dtype)) return mc_conv2d_bf16(g, x0, x1, packed_w, bias, y0, y1, stat_partials, fz, fuse, (hipStream_t)stream);
   return mc_conv2d_f32(g, x0, x1, packed_w, bias, y0, y1, stat_partials, fz, fuse, (hipStream_t)stream);

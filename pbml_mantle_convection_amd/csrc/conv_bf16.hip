@@ -921,7 +921,7 @@ int mc_conv2d_bf16(const ConvGeom& g_in, const void* x0, const void* x1, const v
   int bx = items < cap ? items : cap;
   dim3 grid(bx, groups, 1);
   if (fuse == 2 && g.out_f32) return MC_EUNSUPPORTED;
-  const bool h16 = fuse == 2 ? fz.ey16 != 0 : g.dtype == MC_MIX16;
+  const bool h16 = conv_fuse_h16(g, fz, fuse);
 #define LAUNCH_H(K, TH, TW, NT, MT, F32, FU, H, WN)                                                                    \
   hipLaunchKernelGGL((k_conv_mfma_bf16<K, TH, TW, NT, MT, F32, FU, H, WN>), grid, dim3(64 * (TH * (TW / 16) / (MT)) * (WN)), 0, s, g, \
                      (const bf16_t*)x0, (const bf16_t*)x1, (const bf16_t*)bank, bias, (bf16_t*)y0, (bf16_t*)y1, part,  \

@@ -38,6 +38,23 @@ static inline ConvFuse conv_fuse_none() {
   return f;
 }
 
+// Which instantiation a fused launch takes.  The launches (mc_conv2d_rr, mc_conv2d_bf16) and mc_conv_fused_kernel_name decide
+// through these, so that the name cannot drift from the dispatch.  fuse: 0 none, 1 prologue, 2 epilogue.
+// h16: MC_MIX16 forward launch (f16 operands), or an input-gradient launch whose epilogue reads an f16 y (fz.ey16)
+static inline bool conv_fuse_h16(const ConvGeom& g, const ConvFuse& fz, int fuse) {
+  return fuse == 2 ? fz.ey16 != 0 : g.dtype == MC_MIX16;
+}
+// row reuse: GELU-only instantiations carry the inline polynomial; any other activation takes the generic-switch build
+static inline bool rr_fuse_gelu(const ConvFuse& fz, int fuse) {
+  return fuse == 2 ? fz.eact == MC_ACT_GELU
+                   : ((fz.act0 == MC_ACT_GELU || (fz.act0 == MC_ACT_NONE && !fz.coef0)) &&
+                      (fz.act1 == MC_ACT_GELU || (fz.act1 == MC_ACT_NONE && !fz.coef1)));
+}
+// row reuse: MC_MIX16 + GELU + at most 16 input channels of the launch: the MFMA-side packed-f16 epilogue (DZM)
+static inline bool rr_fuse_dzm(const ConvGeom& g, const ConvFuse& fz, int fuse) {
+  return conv_fuse_h16(g, fz, fuse) && fuse == 2 && rr_fuse_gelu(fz, fuse) && g.CBin <= 2;
+}
+
 // What the DYZ form of the 16-bit filter-gradient kernel (mc_conv2d_wgrad_dz) reads instead of dY, and where it leaves the dY
 // it forms: dY = cA dz + (cB (z - mean) + cC), the expression of k_gn_bwd_apply_dz, per (sample, channel).
 struct WgradDz {
