@@ -1,6 +1,7 @@
 """GPU, kernel level through the C ABI: the ensemble rollout's per-member CFL step, its advection-diffusion step, the stopping
 rule and the six diagnostics (mc_rollout_*), against mc_adnet_step on each member alone at batch 1 (bit equality) and against
-a numpy f64 evaluation of the same f32 fields.  Outputs are NaN-prefilled and sit between sentinel bands."""
+a numpy f64 evaluation of the same f32 fields.  Outputs are NaN-prefilled and sit between sentinel bands.  mc_adnet_step itself
+is held against f64 in tests/test_hip_step_kernels.py; the bit equalities here carry that result over to mc_rollout_step."""
 import functools
 
 import numpy as np
@@ -8,12 +9,22 @@ import pytest
 import torch
 
 import fields
+import step_cases as Sc
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
 SENTINEL = 0xA5
-SIZES = [(3, 5, 6), (2, 9, 70), (4, 33, 130)]      # smallest interior; a row longer than a wave, ragged; several blocks a member
+
+
+class Stretched(int):
+    """A width whose case lives on the stretched, sheared grid of tests/step_cases.py (NaN in the stored wall coordinates)."""
+
+
+# smallest interior; a row longer than a wave, ragged; several blocks a member; 130 x 260: the grid-stride loops run and the 128
+# partials of a member take k_rollout_finalize through its second lane pass
+SIZES = [(3, 5, 6), (2, 9, 70), (4, 33, 130), (2, 130, 260)]
+CASES = SIZES + [pytest.param(4, 33, Stretched(130), id="4-33-130-stretched")]      # and the stretched grid at an existing size
 CN = 0.1
 
 
@@ -46,16 +57,21 @@ def dev(a, dtype=torch.float32):
     return torch.from_numpy(np.ascontiguousarray(a)).to(dtype).to(DEV).contiguous()
 
 
-@functools.lru_cache(maxsize=None)
 def case(B, H, W):
+    return _case(B, H, int(W), isinstance(W, Stretched))
+
+
+@functools.lru_cache(maxsize=None)
+def _case(B, H, W, stretched):
     """Members with different fields, different vel_scale and different RaQ; the LAST member is at rest (u = v = 0)."""
     seed = 100 * B + H
     u = fields.smooth_field(B, H, W, seed + 1) * 2000.0
     v = fields.smooth_field(B, H, W, seed + 2) * 2000.0
     u[B - 1] = 0.0
     v[B - 1] = 0.0
-    xc, yc = grid(H, W)
-    return dict(B=B, H=H, W=W, u=dev(u), v=dev(v), T=dev(fields.temperature_field(B, H, W, seed + 3)),
+    xc, yc = Sc.grid_stretched(H, W) if stretched else grid(H, W)
+    walls = tuple(a.astype(np.float32) for a in Sc.with_walls(xc, yc))            # what the kernels substitute, for the checks
+    return dict(B=B, H=H, W=W, stretched=stretched, grid=walls, u=dev(u), v=dev(v), T=dev(fields.temperature_field(B, H, W, seed + 3)),
                 vs=dev(np.array([0.5, 1.7, 3.0, 0.9])[:B]), raq=dev(np.array([1.5, 2.5, 4.0, 9.0])[:B]), xc=dev(xc), yc=dev(yc))
 
 
@@ -75,10 +91,14 @@ def adnet(c, idx, dt=None):
     return dt_io.cpu()[0], out.t.cpu()
 
 
-@functools.lru_cache(maxsize=None)
 def reference(B, H, W):
+    return _reference(B, H, int(W), isinstance(W, Stretched))
+
+
+@functools.lru_cache(maxsize=None)
+def _reference(B, H, W, stretched):
     """Per member alone at batch 1: its own dt and next T; and the batch-wide dt of the whole batch.  Computed once."""
-    c = case(B, H, W)
+    c = _case(B, H, W, stretched)
     alone = [adnet(c, [b]) for b in range(B)]
     return dict(dt=torch.stack([a[0] for a in alone]), Tn=torch.cat([a[1] for a in alone]), dt_batch=adnet(c, list(range(B)))[0])
 
@@ -118,17 +138,21 @@ def rollout(c, idx, t0=None, t_end=None, steps0=None, n_rows=1, reps=1):
     return {k: b.t.cpu().clone() for k, b in g.items()}
 
 
-@functools.lru_cache(maxsize=None)
 def free_run(B, H, W):
+    return _free_run(B, H, int(W), isinstance(W, Stretched))
+
+
+@functools.lru_cache(maxsize=None)
+def _free_run(B, H, W, stretched):
     """One step of every member from t = 0 with no stopping time.  Computed once, shared, never modified."""
-    return rollout(case(B, H, W), list(range(B)))
+    return rollout(_case(B, H, W, stretched), list(range(B)))
 
 
 def bits(a):
     return a.contiguous().view(torch.int64 if a.dtype == torch.float64 else torch.int32)
 
 
-@pytest.mark.parametrize("B,H,W", SIZES)
+@pytest.mark.parametrize("B,H,W", CASES)
 def test_cfl_step_is_per_member(B, H, W):
     ref, got = reference(B, H, W), free_run(B, H, W)
     dt = got["dt"]
@@ -136,9 +160,7 @@ def test_cfl_step_is_per_member(B, H, W):
     assert torch.equal(bits(dt.float()), bits(ref["dt"])), (dt, ref["dt"])         # bit equality with the member alone
     assert torch.equal(dt.float().double(), dt)                                    # an f32 value held in an f64
     dx = float(got["dxm"][0])
-    xc = grid(H, W)[0]
-    xs = xc.copy()
-    xs[:, 0], xs[:, -1] = 0.0, 4.0
+    xs = case(B, H, W)["grid"][0]                                                  # the case's own grid, walls substituted
     assert dx == float((xs[1:-1, 1:-1] - xs[1:-1, :-2]).min())
     dx2 = np.float32(dx) * np.float32(dx)
     diffusive = np.float32(0.5) * (dx2 * dx2) / (dx2 + dx2)
@@ -151,7 +173,7 @@ def test_cfl_step_is_per_member(B, H, W):
     assert got["t"].tolist() == dt.tolist() and got["steps"].tolist() == [1] * B and got["cursor"].tolist() == [1]
 
 
-@pytest.mark.parametrize("B,H,W", SIZES)
+@pytest.mark.parametrize("B,H,W", CASES)
 def test_step_equals_adnet_on_each_member_alone(B, H, W):
     ref, got = reference(B, H, W), free_run(B, H, W)
     assert not torch.isnan(got["Tn"]).any()
@@ -161,7 +183,7 @@ def test_step_equals_adnet_on_each_member_alone(B, H, W):
     assert torch.equal(got["Tn"][:, :, 0], got["Tn"][:, :, 1]) and torch.equal(got["Tn"][:, :, -1], got["Tn"][:, :, -2])
 
 
-@pytest.mark.parametrize("B,H,W", SIZES)
+@pytest.mark.parametrize("B,H,W", CASES)
 def test_stopping_rule(B, H, W):
     c, ref = case(B, H, W), reference(B, H, W)
     dts = ref["dt"].double()
@@ -193,12 +215,12 @@ def test_stopping_rule(B, H, W):
     assert torch.equal(bits(again["Tn"][0]), bits(c["T"][1].cpu()))
 
 
-@pytest.mark.parametrize("B,H,W", SIZES)
+@pytest.mark.parametrize("B,H,W", CASES)
 def test_diagnostics_against_numpy_f64(B, H, W):
     c, got = case(B, H, W), free_run(B, H, W)
     Tn = got["Tn"].double().numpy()
     u, v, s = c["u"].cpu().double().numpy(), c["v"].cpu().double().numpy(), c["vs"].cpu().double().numpy()
-    yc = grid(H, W)[1].astype(np.float64)
+    yc = c["grid"][1].astype(np.float64)
     h = got["hist"][0].numpy()
     assert np.isfinite(h).all()
     for b in range(B):
@@ -216,7 +238,7 @@ def test_diagnostics_against_numpy_f64(B, H, W):
     assert (h[:B - 1, 3] > 0).all()
 
 
-@pytest.mark.parametrize("B,H,W", SIZES)
+@pytest.mark.parametrize("B,H,W", CASES)
 def test_diagnostics_do_not_depend_on_the_batch(B, H, W):
     c, got = case(B, H, W), free_run(B, H, W)
     twice = rollout(c, list(range(B)))
