@@ -14,8 +14,10 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from dataclasses import dataclass, field
-from typing import Dict, List, Optional, Tuple
+from collections import defaultdict
+from dataclasses import dataclass
+from enum import Enum
+from typing import ClassVar, Dict, List, Optional, Tuple
 
 import numpy as np
 import torch
@@ -523,13 +525,198 @@ class _T:            # runtime tensor
     W: int = 0
     buf: Optional[torch.Tensor] = None
     requires_grad: bool = True
-    gsrcs: list = field(default_factory=list)   # gradient sources registered during backward
     # "normalise on load": the activated tensor is never materialised; consumers read the producer's raw conv output
     # `raw` and apply act(scale * y + shift) from `coef` ([N, CP, 4] table, None = activation only) while staging
     fused: bool = False
     raw: Optional[torch.Tensor] = None
     coef: Optional[torch.Tensor] = None
     act: int = 0
+
+
+@dataclass(frozen=True)
+class Switches:
+    """The MANTLE_* environment switches, read once when an engine is built."""
+    # bit 0: GroupNorm + activation applied by the consumers on load (conv, filter gradient, bicubic) instead of a
+    # stand-alone pass that materialises the activated tensor; bit 1: the GroupNorm-backward reduction fused into the
+    # epilogue of the input-gradient launch (single-consumer tensors).  0 = the round-1 unfused chain (A/B, tests).
+    fuse: int
+    # ... and only for tensors of at most this many pixels.  Measured on MI355X (CFG-3, B = 32): the MFMA kernels
+    # of the two high-resolution levels are bound by vector-instruction issue, so GELU / GELU' evaluated inside them
+    # costs more than the streaming pass it replaces (level-0 16->16 forward 117 -> 207 us against a 100 us pass);
+    # at the deep levels the kernels are launch-latency bound and every fused pass is a launch saved.
+    fuse_maxpix: int
+    # "mixed" mode, round 3: the GroupNorm-backward reduction rides in the input-gradient launch of every eligible layer
+    # whose launch is a row-reuse launch (the wide levels).  y is f16 there, so dz = dA * GELU'(z) and the two sums cost
+    # 8.5 packed-f16 / mixed-precision instructions per element on the loader waves, beside the next stage's MFMAs,
+    # instead of the ~25 f32 instructions that made the same fusion lose in round 2 (DESIGN.md §3).
+    fuse_dz_rr: bool
+    # "mixed" mode: the filter-gradient launch of a layer whose dz comes from its consumer's input-gradient launch forms dY
+    # from (dz, z) while it stages its tiles and stores it, instead of a stand-alone mc_gn_bwd_apply_dz pass
+    # (single-chunk, single-group layers: 10->16 and 16->16).  0 selects the apply pass (A/B).
+    wgrad_dz: bool
+    # GroupNorm + activation of layers with at most this many pixels run as ONE launch per direction (statistics + apply
+    # forward; reduce + finalize + apply backward).  MI355X, CFG-3: 64 x 64 and 32 x 32 layers 21 -> 11 us forward and
+    # 38 -> 24 us backward; 128 x 128 layers break even (25 -> 24, 49 -> 53 us: 128 blocks do not fill the chip)
+    gn_small_pix: int
+
+    @classmethod
+    def read(cls, precision):
+        env, mixed = os.environ.get, precision == "mixed"
+        return cls(int(env("MANTLE_FUSE", "0")), int(env("MANTLE_FUSE_MAXPIX", str(128 * 128))),
+                   mixed and env("MANTLE_FUSE_DZ_RR", "1") != "0", mixed and env("MANTLE_WGRAD_DZ", "1") != "0",
+                   int(env("MANTLE_GN_SMALL_PIX", str(64 * 64 + 4))))
+
+
+# Routes: every choice between launches, made once by Engine._route before a buffer exists (DESIGN.md §1, "The engine's plan and routes")
+class GnFwd(Enum):           # what follows a layer's conv launch
+    NONE = "none"            # the final conv: nothing
+    MEANS = "means"          # the final conv of a subtract_mean graph: its channel means (mc_gn_finalize)
+    SMALL = "small"          # statistics + activation (+ pooling) in one launch (mc_gn_act_fwd_small)
+    APPLY = "apply"          # mc_gn_finalize_coef (GroupNorm layers), then mc_gn_act_fwd
+    FUSED = "fused"          # mc_gn_finalize_coef; consumers normalise on load, only a pooled tensor is materialised
+
+
+class GnBwd(Enum):           # how a layer's dY is formed from the gradient of its activated output
+    NONE = "none"            # the final conv: dY is the packed output gradient
+    SMALL = "small"          # reduce + finalize + apply in one launch (mc_gn_act_bwd_small)
+    APPLY = "apply"          # mc_gn_act_bwd_reduce + _finalize (GroupNorm layers), then mc_gn_act_bwd_apply
+    DZ_APPLY = "dz_apply"    # dz and its sums came from the consumer's input-gradient launch: finalize + mc_gn_bwd_apply_dz
+    DZ_WGRAD = "dz_wgrad"    # ... finalize_dz, and the filter-gradient launch forms dY (mc_conv2d_wgrad_dz)
+
+
+class UpBwd(Enum):           # the bicubic adjoint
+    WALK = "walk"
+    TAPS = "taps"
+    SEPARABLE = "separable"
+
+
+DZ_ROUTES = (GnBwd.DZ_APPLY, GnBwd.DZ_WGRAD)
+
+
+@dataclass(frozen=True)
+class ConvRoute:
+    need_part: bool          # the conv launch (or the pass after it) leaves per-tile sums of Y
+    fused: bool              # the activated output is never materialised (_T.fused)
+    gn_fwd: GnFwd
+    gn_bwd: GnBwd
+    epi: int = -1            # node index of the producer whose GroupNorm-backward reduction this layer's input-gradient launch carries
+    dz_tiles: int = 0        # dz routes: partial-sum slots the consumer's conv tiles / conv tiles + fold blocks write
+    dz_blocks: int = 0
+    dz_n: bool = False       # dz routes: the finalize with one block per (group, sample) (_n), many slots per sample
+    tiles: int = 0           # fixed-padding convs: tiles of the forward launch (<= 0: an unsupported configuration)
+
+
+@dataclass(frozen=True)
+class UpRoute:
+    bwd: UpBwd
+    maxtaps: Tuple[int, int]  # longest transposed tap list along y, x
+
+
+@dataclass(slots=True, kw_only=True)
+class LayerPlan:
+    """What the three kinds of conv layer share: the raw output, its partial sums and the GroupNorm buffers of its route."""
+    node: ConvNode
+    route: ConvRoute
+    tiles: int                               # partial-sum slots per sample
+    coutp: int
+    Y: torch.Tensor
+    part: torch.Tensor
+    need_dgrad: bool
+    stats: Optional[torch.Tensor] = None     # GroupNorm layers: (mean, rstd) per (sample, group)
+    m12: Optional[torch.Tensor] = None       # ... backward APPLY and the dz routes
+    gpart: Optional[torch.Tensor] = None     # ... backward APPLY: per-block sums of the stand-alone reduction
+
+
+@dataclass(slots=True, kw_only=True)
+class ConvPlan(LayerPlan):
+    op: ClassVar[str] = "conv"
+    desc: L.ConvDesc
+    ddesc: Optional[L.ConvDesc]
+    bank: torch.Tensor
+    wpart: torch.Tensor                      # filter-gradient partial slabs: ONE batched launch combines all layers'
+    dbank: Optional[torch.Tensor] = None
+    dxp: tuple = ()                          # input gradients on the padded domain, one per source
+    coef: Optional[torch.Tensor] = None      # GroupNorm layers: (scale, shift, mean, rstd); padded channels stay 0
+    pc: Optional[torch.Tensor] = None        # backward SMALL: per-channel sums for the batched dgamma / dbeta launch
+    dz_part: Optional[torch.Tensor] = None   # dz routes: what the consumer's launch reduces into
+    dz_pc: Optional[torch.Tensor] = None     # ... with the _n finalize
+    dz_coef: Optional[torch.Tensor] = None   # DZ_WGRAD: (cA, cB, cC, mean) per (sample, channel); padded channels stay 0
+
+
+@dataclass(slots=True, kw_only=True)
+class LearnedPlan(LayerPlan):
+    op: ClassVar[str] = "learned"
+    ldesc: L.LearnedDesc
+    desc: L.ConvDesc                         # the valid convolution on the whole input
+    fdesc: L.ConvDesc                        # the main bank as launched forward (desc, or zero-padded straight into Y)
+    ddesc: L.ConvDesc
+    fy: int
+    fx: int
+    mh: int
+    mw: int
+    R: Optional[torch.Tensor]                # the valid result, where it has to be placed with mc_rect_copy
+    dR: torch.Tensor
+    dxl: Optional[torch.Tensor]
+    bank: torch.Tensor
+    dbank: Optional[torch.Tensor]
+    wpart: torch.Tensor
+    lbank: torch.Tensor
+    ldbank: Optional[torch.Tensor]
+    lws_bytes: int
+
+
+@dataclass(slots=True, kw_only=True)
+class SpectralPlan(LayerPlan):
+    op: ClassVar[str] = "spectral"
+    tabs: tuple
+    apart: torch.Tensor                      # per-slot mode sums of the input / of dY
+    xhat: torch.Tensor                       # modes of the input, kept for the backward pass
+    mcoef: torch.Tensor                      # coefficients of the output / of the input gradient
+    gbuf: torch.Tensor
+    dxl: Optional[torch.Tensor]
+
+
+@dataclass(slots=True, kw_only=True)
+class UpPlan:
+    op: ClassVar[str] = "up"
+    node: UpNode
+    route: UpRoute
+    tabs: tuple
+    dsrc: torch.Tensor
+    bws: Optional[torch.Tensor] = None       # SEPARABLE: the f32 workspace between the two 1-D passes
+
+
+@dataclass(slots=True, kw_only=True)
+class PoolPlan:
+    op: ClassVar[str] = "pool"
+    node: PoolNode
+    dsum: torch.Tensor
+
+
+@dataclass(slots=True, kw_only=True)
+class CatPlan:
+    op: ClassVar[str] = "cat"
+    node: CatNode
+    gather: dict                             # tensor id -> (first channel, gradient buffer) of the operands gathered in backward
+
+
+class _Backward:
+    """The state of one backward call: what every tensor's gradient is read from, and the dz a consumer's input-gradient
+    launch left for its producer.  Nothing of it outlives the call."""
+
+    def __init__(self, params, grads, st):
+        self.params, self.grads, self.st = params, grads, st
+        self.srcs: Dict[int, list] = defaultdict(list)      # tensor id -> GradSrc list
+        self.dz: Dict[int, L.GradSrc] = {}                   # output tensor id of the producer -> its dz
+        self.gp_jobs = []                                    # GroupNorm parameter gradients of the one-launch layers
+
+    def plain(self, tid, buf, t):
+        self.srcs[tid].append(L.GradSrc(L.ptr(buf), L.GSRC_PLAIN, 0, 0, 1, t.H, t.W))
+
+
+def _columns(rows, *types):
+    """A list of job tuples as parallel ctypes arrays, one per column."""
+    return [(t * len(rows))(*[r[k] for r in rows]) for k, t in enumerate(types)]
 
 
 class Engine:
@@ -546,29 +733,11 @@ class Engine:
         # gradient tensors: bf16 in the "mixed" mode (their range), the forward type otherwise
         self.mc_gdtype, self.g_dtype = (L.MC_BF16, torch.bfloat16) if self.mc_dtype == L.MC_MIX16 else (self.mc_dtype, self.t_dtype)
         self.shape = None
+        self._frozen = False
         self._tables = {}
-        # bit 0: GroupNorm + activation applied by the consumers on load (conv, filter gradient, bicubic) instead of a
-        # stand-alone pass that materialises the activated tensor; bit 1: the GroupNorm-backward reduction fused into the
-        # epilogue of the input-gradient launch (single-consumer tensors).  0 = the round-1 unfused chain (A/B, tests).
-        self.fuse = int(os.environ.get("MANTLE_FUSE", "0"))
-        # ... and only for tensors of at most this many pixels.  Measured on MI355X (CFG-3, B = 32): the MFMA kernels
-        # of the two high-resolution levels are bound by vector-instruction issue, so GELU / GELU' evaluated inside them
-        # costs more than the streaming pass it replaces (level-0 16->16 forward 117 -> 207 us against a 100 us pass);
-        # at the deep levels the kernels are launch-latency bound and every fused pass is a launch saved.
-        self.fuse_maxpix = int(os.environ.get("MANTLE_FUSE_MAXPIX", str(128 * 128)))
-        # "mixed" mode, round 3: the GroupNorm-backward reduction rides in the input-gradient launch of every eligible layer
-        # whose launch is a row-reuse launch (the wide levels).  y is f16 there, so dz = dA * GELU'(z) and the two sums cost
-        # 8.5 packed-f16 / mixed-precision instructions per element on the loader waves, beside the next stage's MFMAs,
-        # instead of the ~25 f32 instructions that made the same fusion lose in round 2.
-        self.fuse_dz_rr = precision == "mixed" and os.environ.get("MANTLE_FUSE_DZ_RR", "1") != "0"
-        # "mixed" mode: the filter-gradient launch of a layer whose dz comes from its consumer's input-gradient launch forms dY
-        # from (dz, z) while it stages its tiles and stores it, instead of a stand-alone mc_gn_bwd_apply_dz pass
-        # (single-chunk, single-group layers: 10->16 and 16->16).  0 selects the apply pass (A/B).
-        self.wgrad_dz = precision == "mixed" and os.environ.get("MANTLE_WGRAD_DZ", "1") != "0"
-        # GroupNorm + activation of layers with at most this many pixels run as ONE launch per direction (statistics + apply
-        # forward; reduce + finalize + apply backward).  MI355X, CFG-3: 64 x 64 and 32 x 32 layers 21 -> 11 us forward and
-        # 38 -> 24 us backward; 128 x 128 layers break even (25 -> 24, 49 -> 53 us: 128 blocks do not fill the chip)
-        self.gn_small_pix = int(os.environ.get("MANTLE_GN_SMALL_PIX", str(64 * 64 + 4)))
+        self.sw = Switches.read(precision)
+        self.plan, self.convs, self.learned, self.spectral = [], [], [], []
+        self._probe, self._probe_pool = None, []
         # dropout (graphs with drop nodes only): the device state (seed_lo, seed_hi, step, 0) is allocated in configure();
         # the seed is kept here so that it survives a re-plan
         self.has_drop = any(n.kind == "conv" and n.drop > 0 for n in graph.nodes)
@@ -576,6 +745,8 @@ class Engine:
         self._drop_seed = 0
         self._drop_step = 0                  # a step set before configure() allocated drop_state: written there
         self._drop_on = False                # whether the last forward ran with dropout (its backward follows it)
+
+    fuse = property(lambda self: self.sw.fuse)
 
     # -------------------------------------------------------------- dropout state
     def set_dropout_seed(self, seed: int):
@@ -604,11 +775,12 @@ class Engine:
         """The 64-bit seed as set (the device state holds its two words)."""
         return self._drop_seed
 
-    def _drop_desc(self, node):
-        """mc_dropout of a node in a dropout pass, else None."""
+    def _drop(self, node):
+        """(entry-name suffix, trailing arguments) of a launch on this node's output: ("_drop", (mc_dropout,)) in a dropout
+        pass of a dropout node -- backward regenerates the forward's mask from the same (seed, step, layer) -- else ("", ())."""
         if not (self._drop_on and node.drop > 0):
-            return None
-        return L.Dropout(L.ptr(self.drop_state), node.layer, L.dropout_keep16(node.drop))
+            return "", ()
+        return "_drop", (C.byref(L.Dropout(L.ptr(self.drop_state), node.layer, L.dropout_keep16(node.drop))),)
 
     # -------------------------------------------------------------- planning
     def freeze(self):
@@ -616,10 +788,20 @@ class Engine:
         batch / grid size would leave the graph replaying freed memory.  Further calls with a different shape raise."""
         self._frozen = True
 
+    def _cb8(self, c, h, w, grad=False):
+        """An activation tensor (grad: a gradient tensor) in the CB8 layout."""
+        return torch.empty((self.N, (c + 7) // 8, h, w, 8), dtype=self.g_dtype if grad else self.t_dtype, device=self.device)
+
+    def _f32(self, *shape, zero=False):
+        return (torch.zeros if zero else torch.empty)(shape, dtype=torch.float32, device=self.device)
+
+    def _u8(self, nbytes):
+        return torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+
     def configure(self, N: int, H: int, W: int, device):
         if self.shape == (N, H, W, str(device)):
             return
-        if getattr(self, "_frozen", False):
+        if self._frozen:
             raise RuntimeError(f"this engine is pinned to input shape {self.shape[:3]} by a captured HIP graph; got {(N, H, W)} "
                                "(use a separate module / engine instance, or an un-captured trainer, for another shape)")
         g = self.g
@@ -627,176 +809,192 @@ class Engine:
             raise ValueError(f"input H, W must be divisible by {g.divisor}")
         self.device = device
         self.N = N
-        size, grad, convs = shape_walk(g, N, H, W, self.precision)
-        T: Dict[int, _T] = {tid: _T(C=c, H=size[tid][0], W=size[tid][1], requires_grad=grad[tid])
-                            for tid, c in g.channels.items()}
+        size, grad, shapes = shape_walk(g, N, H, W, self.precision)
+        self.T = T = {tid: _T(C=c, H=size[tid][0], W=size[tid][1], requires_grad=grad[tid]) for tid, c in g.channels.items()}
         self.mode = L.PAD_MODES[g.pad_mode]
-        f32 = dict(dtype=torch.float32, device=device)
-        self.plan = []
-        max_dy = 0
-
-        def cb8(c, h, w):
-            return torch.empty((N, (c + 7) // 8, h, w, 8), dtype=self.t_dtype, device=device)
-
-        def cb8g(c, h, w):                   # a gradient tensor
-            return torch.empty((N, (c + 7) // 8, h, w, 8), dtype=self.g_dtype, device=device)
-
-        T[0].buf = cb8(T[0].C, T[0].H, T[0].W)
         # consumers of every tensor (decides which activated tensors need not be materialised)
-        cons: Dict[int, list] = {tid: [] for tid in g.channels}
+        self.cons = {tid: [] for tid in g.channels}
         for node in g.nodes:
             for i in (node.srcs if node.kind in ("conv", "cat") else [node.src]):
-                cons[i].append(node)
-        self.cons = cons
-        self.prod = {}                       # tensor id -> plan entry of the conv that produced it (full-resolution output)
+                self.cons[i].append(node)
+        routes = self._route(size, shapes)   # every choice between launches, before the first buffer
+        T[0].buf = self._cb8(T[0].C, T[0].H, T[0].W)
+        self.plan = []
+        self.prod = {}                       # tensor id -> plan record of the conv that produced it (full-resolution output)
+        max_dy = 0
         for i, node in enumerate(g.nodes):
-            if node.kind == "up":
-                s, o = T[node.src], T[node.out]
-                o.buf = cb8(o.C, o.H, o.W)
-                tabs = (self._table(s.H, o.H), self._table(s.W, o.W))
-                e = dict(node=node, tabs=tabs, dsrc=cb8g(s.C, s.H, s.W),
-                         maxtaps=tuple(int(np.diff(bicubic_tables(a, b)[2]).max()) for a, b in ((s.H, o.H), (s.W, o.W))))
-                if o.H > 3 * s.H or o.W > 3 * s.W:
-                    # scale factor > 3: the adjoint runs as two 1-D passes through an f32 workspace (tap lists too long
-                    # for the tiled kernel's window)
-                    e["bws"] = torch.empty((N, (s.C + 7) // 8, s.H, o.W, 8), **f32)
-                self.plan.append(e)
-                continue
-            if node.kind == "pool":
+            if node.kind == "conv":
                 o = T[node.out]
-                o.buf = cb8(o.C, o.H, o.W)
-                self.plan.append(dict(node=node, dsum=cb8g(o.C, o.H, o.W)))
-                continue
-            if node.kind == "cat":
-                o = T[node.out]
-                o.buf = cb8(o.C, o.H, o.W)
-                # backward: an operand that is exactly its own channel blocks of the concat (starts on a block boundary, and
-                # is the last operand or fills whole blocks) reads its slice of the concat's gradient in place; any other
-                # gets a buffer of its own, gathered by mc_cat_grad_gather (offset: the operand's first channel)
-                gather, off = {}, 0
-                for k, t in enumerate(node.srcs):
-                    c = T[t].C
-                    if T[t].requires_grad and (off % 8 or (k < len(node.srcs) - 1 and c % 8)):
-                        gather[t] = (off, cb8g(c, o.H, o.W))
-                    off += c
-                self.plan.append(dict(node=node, gather=gather))
-                continue
-            o = T[node.out]
-            plan = self._plan_spectral if node.spectral else self._plan_learned if node.learned else self._plan_conv
-            e = plan(node, convs[i], [T[t] for t in node.srcs], o, cb8, cb8g, f32)
-            if node.pool > 1:
-                T[node.pooled].buf = cb8(node.c_out, T[node.pooled].H, T[node.pooled].W)
-            max_dy = max(max_dy, N * e["coutp"] * o.H * o.W)
+                plan = self._plan_spectral if node.spectral else self._plan_learned if node.learned else self._plan_conv
+                e = plan(node, shapes[i], routes[i], [T[t] for t in node.srcs], o)
+                if not o.fused:              # the activated output; a layer without activation: its raw output
+                    o.buf = self._cb8(node.c_out, o.H, o.W) if node.post != L.POST_NONE else e.Y
+                if node.pool > 1:
+                    T[node.pooled].buf = self._cb8(node.c_out, T[node.pooled].H, T[node.pooled].W)
+                max_dy = max(max_dy, N * e.coutp * o.H * o.W)
+            else:
+                T[node.out].buf = self._cb8(T[node.out].C, T[node.out].H, T[node.out].W)
+                e = self._plan_up(node, routes[i]) if node.kind == "up" else getattr(self, "_plan_" + node.kind)(node)
             self.plan.append(e)
-        self.T = T
         # one output-gradient buffer for every layer: backward is one stream, so a layer's filter- and input-gradient
         # launches have read it before the next layer down writes its own
         self.dY = torch.empty(max_dy, dtype=self.g_dtype, device=device)
-        self.convs = [e for e in self.plan if e["node"].kind == "conv" and not e["node"].learned and not e["node"].spectral]
-        self.learned = [e for e in self.plan if e["node"].kind == "conv" and e["node"].learned]
-        self.spectral = [e for e in self.plan if e["node"].kind == "conv" and e["node"].spectral]
+        self.convs = [e for e in self.plan if e.op == "conv"]
+        self.learned = [e for e in self.plan if e.op == "learned"]
+        self.spectral = [e for e in self.plan if e.op == "spectral"]
         # one filter-gradient workspace for the frames of every learned layer (backward is one stream)
-        self.lws = torch.empty(max([e["lws_bytes"] for e in self.learned] + [0]), dtype=torch.uint8, device=device)
-        last = self.plan[-1]
-        assert last["node"].kind == "conv", "graph must end in a conv node"
-        self.final_plain = last["node"].post == L.POST_NONE
+        self.lws = self._u8(max([e.lws_bytes for e in self.learned] + [0]))
+        last = self.plan[-1].node
+        assert last.kind == "conv", "graph must end in a conv node"
+        self.final_plain = last.post == L.POST_NONE
         assert self.final_plain or not g.subtract_mean
-        fo = T[last["node"].out]
+        fo = T[last.out]
         self.out_h, self.out_w = fo.H, fo.W - 2 * g.crop_w
-        self.dOut = None if self.final_plain else cb8g(fo.C, fo.H, fo.W)
-        self.chan_mean = torch.empty((N, g.c_out), **f32) if g.subtract_mean else None
-        self.gmean = torch.empty((N, g.c_out), **f32) if g.subtract_mean else None
+        self.dOut = None if self.final_plain else self._cb8(fo.C, fo.H, fo.W, grad=True)
+        self.chan_mean = self._f32(N, g.c_out) if g.subtract_mean else None
+        self.gmean = self._f32(N, g.c_out) if g.subtract_mean else None
         if self.has_drop:
             self.drop_state = torch.zeros(4, dtype=torch.int32, device=device)
             self._write_drop_state(self._drop_step)      # (0 unless a restored step waited for this allocation)
         self.shape = (N, H, W, str(device))
 
-    def _plan_gn(self, e, node, o, f32):
-        """GroupNorm statistics and the buffers of the stand-alone backward reduction, for either kind of conv layer."""
-        N = self.N
-        e["stats"] = torch.empty((N, node.groups, 2), **f32)
-        e["gblocks"] = L.call("mc_gn_bwd_blocks", o.H, o.W)
-        e["gpart"] = torch.empty((N, e["gblocks"], e["coutp"], 2), **f32)
-        e["m12"] = torch.empty((N, node.groups, 2), **f32)
-
-    def _plan_conv(self, node, shape, srcs, o, cb8, cb8g, f32):
-        """A convolution with fixed padding over one or two sources: its buffers, whether its activated output is materialised
-        (o.fused) and whether its input-gradient launch carries the source layer's GroupNorm-backward reduction (e["epi"])."""
-        g, N, device = self.g, self.N, self.device
-        h, w, ho, wo = srcs[0].H, srcs[0].W, o.H, o.W
-        d, dd, final_f32 = shape.d, shape.dd, shape.final_f32
-        tiles = L.call("mc_conv_tiles", C.byref(d))
-        if tiles <= 0:
-            raise L.MantleHipError(f"unsupported convolution configuration for {node.name} "
-                                   f"({self.precision}, c_in={srcs[0].C}+{d.c_in1}, c_out={node.c_out}, k={node.k})")
-        coutp = ((node.c_out + 7) // 8) * 8
-        e = dict(node=node, desc=d, ddesc=dd, tiles=tiles, coutp=coutp,
-                 Y=(torch.empty((N, (node.c_out + 7) // 8, ho, wo, 8), dtype=torch.float32, device=device)
-                    if final_f32 else cb8(node.c_out, ho, wo)),
-                 part=torch.empty((N, tiles, coutp, 2), **f32),
-                 bank=torch.empty(L.call("mc_packed_weight_bytes", C.byref(d), 0), dtype=torch.uint8, device=device),
-                 need_dgrad=shape.dgrad)
-        # this layer's filter-gradient launch may form dY from dz itself (mc_conv2d_wgrad_dz: "mixed", one input-channel chunk,
-        # one output-channel group, sources read as they are); whether it does is settled where its dz is planned, below
-        e["wdz_ok"] = (self.wgrad_dz and self.mc_dtype == L.MC_MIX16 and node.post == L.POST_GN_ACT and node.c_out <= 16
-                       and sum((s.C + 7) // 8 for s in srcs) <= 2 and not any(s.fused for s in srcs))
-        cons = self.cons[node.out]
-        fusable = all(c.kind == "up" or (c.kind == "conv" and not c.learned and not c.spectral) for c in cons)
-        o.fused = bool((self.fuse & 1) and node.post != L.POST_NONE and fusable and (cons or node.pool > 1)
-                       and ho * wo <= self.fuse_maxpix and not node.drop)      # (a dropout layer's output is materialised)
-        if o.fused:
-            o.raw, o.act = e["Y"], L.ACTS[g.act]
-        elif node.post != L.POST_NONE:
-            o.buf = cb8(node.c_out, ho, wo)
-        else:
-            o.buf = e["Y"]
-        self.prod[node.out] = e
-        if node.post == L.POST_GN_ACT:
-            self._plan_gn(e, node, o, f32)
-            e["coef"] = torch.zeros((N, coutp, 4), **f32)       # (scale, shift, mean, rstd); padded channels stay 0
-            if o.fused:
-                o.coef = e["coef"]
-            # small layers: reduce + finalize + apply of the GroupNorm backward in one launch (mc_gn_act_bwd_small)
-            if ho * wo <= self.gn_small_pix and (node.c_out // node.groups) in (1, 2, 4, 8):
-                e["pc"] = torch.empty((N, coutp, 2), **f32)
-        if shape.dgrad:
-            e["dbank"] = torch.empty(L.call("mc_packed_weight_bytes", C.byref(d), 1), dtype=torch.uint8, device=device)
-            hp, wp = h + 2 * node.pad, w + 2 * node.pad
-            e["dxp"] = [cb8g(s.C, hp, wp) for s in srcs]
-            # GroupNorm-backward reduction fused into this launch's epilogue: the source is the full-resolution output
-            # of a conv + (GN) + act layer and this conv is its only consumer
-            pe = self.prod.get(node.srcs[0])
-            dz_here = bool(self.fuse & 2) and h * w <= self.fuse_maxpix
-            if (not dz_here and self.fuse_dz_rr and g.act == "gelu"
+    def _route(self, size, shapes):
+        """The routing pass: node index -> ConvRoute / UpRoute for the whole graph, from the shapes, the switches and the
+        library's host queries alone.  It runs before any buffer is allocated, so that "my consumer's input-gradient launch
+        takes my reduction" is an input to a layer's own route; forward and backward switch on what it decides."""
+        g, sw, ch = self.g, self.sw, self.g.channels
+        routes, fused, prod, wdz_ok, epi, dz, tiles = {}, set(), {}, {}, {}, {}, {}
+        for i, node in enumerate(g.nodes):
+            if node.kind == "up":
+                (h, w), (ho, wo) = size[node.src], size[node.out]
+                maxtaps = tuple(int(np.diff(bicubic_tables(a, b)[2]).max()) for a, b in ((h, ho), (w, wo)))
+                # scale factor > 3: the adjoint runs as two 1-D passes through an f32 workspace (tap lists too long
+                # for the tiled kernel's window)
+                sep = ho > 3 * h or wo > 3 * w
+                routes[i] = UpRoute(UpBwd.SEPARABLE if sep else UpBwd.WALK if maxtaps[1] <= 12 else UpBwd.TAPS, maxtaps)
+            if node.kind != "conv" or node.learned or node.spectral:
+                continue
+            tiles[i] = L.call("mc_conv_tiles", C.byref(shapes[i].d))
+            if tiles[i] <= 0:                # _plan_conv raises when it comes to this node
+                continue
+            (h, w), (ho, wo), dd = size[node.srcs[0]], size[node.out], shapes[i].dd
+            # this layer's filter-gradient launch may form dY from dz itself (mc_conv2d_wgrad_dz: "mixed", one input-channel
+            # chunk, one output-channel group, sources read as they are), if its consumer leaves it a dz (below)
+            wdz_ok[i] = (sw.wgrad_dz and self.mc_dtype == L.MC_MIX16 and node.post == L.POST_GN_ACT and node.c_out <= 16
+                         and sum((ch[t] + 7) // 8 for t in node.srcs) <= 2 and not any(t in fused for t in node.srcs))
+            cons = self.cons[node.out]
+            fusable = all(c.kind == "up" or (c.kind == "conv" and not c.learned and not c.spectral) for c in cons)
+            if ((sw.fuse & 1) and node.post != L.POST_NONE and fusable and (cons or node.pool > 1)
+                    and ho * wo <= sw.fuse_maxpix and not node.drop):      # (a dropout layer's output is materialised)
+                fused.add(node.out)
+            prod[node.out] = i
+            # GroupNorm-backward reduction fused into this layer's input-gradient epilogue: the source is the full-resolution
+            # output of a conv + (GN) + act layer and this conv is its only consumer
+            p = prod.get(node.srcs[0])
+            if dd is None or p is None:
+                continue
+            dz_here = bool(sw.fuse & 2) and h * w <= sw.fuse_maxpix
+            if (not dz_here and sw.fuse_dz_rr and g.act == "gelu"
                     and L.load().mc_conv_kernel_name(C.byref(dd)).decode().startswith("k_conv_rr")):
                 dz_here = True
-            if (dz_here and len(srcs) == 1 and pe is not None and pe["node"].post != L.POST_NONE
-                    and not pe["node"].learned and not pe["node"].spectral and len(self.cons[node.srcs[0]]) == 1 and pe["node"].pool == 1
-                    and not pe["node"].drop):       # (the epilogue's dz = dA act'(z) knows no mask)
+            pn = g.nodes[p]
+            if (dz_here and len(node.srcs) == 1 and pn.post != L.POST_NONE and not pn.learned and not pn.spectral
+                    and len(self.cons[node.srcs[0]]) == 1 and pn.pool == 1
+                    and not pn.drop):               # (the epilogue's dz = dA act'(z) knows no mask)
                 dtiles = L.call("mc_conv_tiles", C.byref(dd))
-                fblocks = L.call("mc_fold_blocks", h, w, node.pad, self.mode)
-                e["epi"] = pe
-                pe["dz_tiles"], pe["dz_blocks"] = dtiles, dtiles + fblocks
-                pe["dz_part"] = torch.empty((N, dtiles + fblocks, pe["coutp"], 2), **f32)
-                if "m12" not in pe and pe["node"].post == L.POST_GN_ACT:
-                    pe["m12"] = torch.empty((N, pe["node"].groups, 2), **f32)
-                if (pe["node"].post == L.POST_GN_ACT and pe["dz_blocks"] > 256
-                        and (pe["node"].c_out // pe["node"].groups) in (1, 2, 4, 8)):
-                    pe["dz_pc"] = torch.empty((N, pe["coutp"], 2), **f32)
-                if pe.get("wdz_ok"):
-                    # no apply launch: the finalize writes (cA, cB, cC, mean) per (sample, channel), the filter-gradient
-                    # launch forms dY from (dz, z) and stores it for the input-gradient launch (padded channels stay 0)
-                    pe["dz_coef"] = torch.zeros((N, pe["coutp"], 4), **f32)
-        # per-layer filter-gradient partial slabs: all layers are combined by ONE batched launch at the end of backward
-        e["wpart"] = torch.empty(L.call("mc_wgrad_partial_bytes", C.byref(d)), dtype=torch.uint8, device=device)
+                epi[i], dz[p] = p, (dtiles, dtiles + L.call("mc_fold_blocks", h, w, node.pad, self.mode))
+        for i, node in enumerate(g.nodes):
+            if node.kind != "conv":
+                continue
+            (ho, wo), gn, final = size[node.out], node.post == L.POST_GN_ACT, node.post == L.POST_NONE
+            pow2 = gn and (node.c_out // node.groups) in (1, 2, 4, 8)
+            dz_tiles, dz_blocks = dz.get(i, (0, 0))
+            # small layers: the GroupNorm backward (and, below, the forward) in one launch
+            small = pow2 and ho * wo <= sw.gn_small_pix and not node.learned and not node.spectral
+            if small and node.out not in fused and node.pool in (1, 2) and (sw.fuse == 0 or sw.fuse_dz_rr) and i not in dz:
+                fwd = GnFwd.SMALL
+            elif final:
+                fwd = GnFwd.MEANS if g.subtract_mean else GnFwd.NONE
+            else:
+                fwd = GnFwd.FUSED if node.out in fused else GnFwd.APPLY
+            if final:
+                bwd = GnBwd.NONE
+            elif i in dz:
+                bwd = GnBwd.DZ_WGRAD if wdz_ok[i] else GnBwd.DZ_APPLY
+            else:
+                bwd = GnBwd.SMALL if small else GnBwd.APPLY
+            routes[i] = ConvRoute(need_part=gn or (final and g.subtract_mean), fused=node.out in fused, gn_fwd=fwd, gn_bwd=bwd,
+                                  epi=epi.get(i, -1), dz_tiles=dz_tiles, dz_blocks=dz_blocks,
+                                  dz_n=pow2 and dz_blocks > 256,      # many slots per sample: one block per (group, sample)
+                                  tiles=tiles.get(i, 0))
+        return routes
+
+    def _plan_gn(self, node, o, route, coutp):
+        """GroupNorm statistics and the buffers of the backward form the route names, for any kind of conv layer."""
+        if node.post != L.POST_GN_ACT:
+            return {}
+        N, bwd = self.N, route.gn_bwd
+        return dict(stats=self._f32(N, node.groups, 2), m12=self._f32(N, node.groups, 2) if bwd is not GnBwd.SMALL else None,
+                    gpart=self._f32(N, L.call("mc_gn_bwd_blocks", o.H, o.W), coutp, 2) if bwd is GnBwd.APPLY else None)
+
+    def _plan_up(self, node, route):
+        s, o = self.T[node.src], self.T[node.out]
+        return UpPlan(node=node, route=route, tabs=(self._table(bicubic_tables, s.H, o.H), self._table(bicubic_tables, s.W, o.W)),
+                      dsrc=self._cb8(s.C, s.H, s.W, grad=True),
+                      bws=self._f32(self.N, (s.C + 7) // 8, s.H, o.W, 8) if route.bwd is UpBwd.SEPARABLE else None)
+
+    def _plan_pool(self, node):
+        o = self.T[node.out]
+        return PoolPlan(node=node, dsum=self._cb8(o.C, o.H, o.W, grad=True))
+
+    def _plan_cat(self, node):
+        """backward: an operand that is exactly its own channel blocks of the concat (starts on a block boundary, and is the
+        last operand or fills whole blocks) reads its slice of the concat's gradient in place; any other gets a buffer of
+        its own, gathered by mc_cat_grad_gather (offset: the operand's first channel)."""
+        T, o = self.T, self.T[node.out]
+        gather, off = {}, 0
+        for k, t in enumerate(node.srcs):
+            c = T[t].C
+            if T[t].requires_grad and (off % 8 or (k < len(node.srcs) - 1 and c % 8)):
+                gather[t] = (off, self._cb8(c, o.H, o.W, grad=True))
+            off += c
+        return CatPlan(node=node, gather=gather)
+
+    def _plan_conv(self, node, shape, route, srcs, o):
+        """A convolution with fixed padding over one or two sources: the buffers of its route."""
+        N, d, coutp, gn = self.N, shape.d, ((node.c_out + 7) // 8) * 8, node.post == L.POST_GN_ACT
+        h, w, ho, wo = srcs[0].H, srcs[0].W, o.H, o.W
+        tiles = route.tiles
+        if tiles <= 0:
+            raise L.MantleHipError(f"unsupported convolution configuration for {node.name} "
+                                   f"({self.precision}, c_in={d.c_in0}+{d.c_in1}, c_out={node.c_out}, k={node.k})")
+        dz = route.gn_bwd in DZ_ROUTES
+        e = ConvPlan(node=node, route=route, desc=d, ddesc=shape.dd, tiles=tiles, coutp=coutp,
+                     Y=self._f32(N, (node.c_out + 7) // 8, ho, wo, 8) if shape.final_f32 else self._cb8(node.c_out, ho, wo),
+                     part=self._f32(N, tiles, coutp, 2), bank=self._u8(L.call("mc_packed_weight_bytes", C.byref(d), 0)),
+                     need_dgrad=shape.dgrad, wpart=self._u8(L.call("mc_wgrad_partial_bytes", C.byref(d))),
+                     coef=self._f32(N, coutp, 4, zero=True) if gn else None,
+                     pc=self._f32(N, coutp, 2) if route.gn_bwd is GnBwd.SMALL else None,
+                     dz_part=self._f32(N, route.dz_blocks, coutp, 2) if dz else None,
+                     dz_pc=self._f32(N, coutp, 2) if route.dz_n else None,
+                     dz_coef=self._f32(N, coutp, 4, zero=True) if route.gn_bwd is GnBwd.DZ_WGRAD else None,
+                     **self._plan_gn(node, o, route, coutp))
+        if shape.dgrad:
+            hp, wp = h + 2 * node.pad, w + 2 * node.pad
+            e.dbank = self._u8(L.call("mc_packed_weight_bytes", C.byref(d), 1))
+            e.dxp = tuple(self._cb8(s.C, hp, wp, grad=True) for s in srcs)
+        o.fused = route.fused
+        if o.fused:
+            o.raw, o.coef, o.act = e.Y, e.coef, L.ACTS[self.g.act]
+        self.prod[node.out] = e
         return e
 
     # -------------------------------------------------------------- learned padding (BoundaryLearnedConvolution2D)
-    def _plan_learned(self, node, shape, srcs, o, cb8, cb8g, f32):
+    def _plan_learned(self, node, shape, route, srcs, o):
         """The main bank on the library's conv kernels, the frame of the eight border banks on the mc_learned_frame_* kernels,
         which read the input / the output gradient in place (reference pytorch_networks_convae.py:1022-1065).  The gradient
         w.r.t. the input needs no padded domain: the adjoint of a valid convolution is exactly input-sized."""
-        (s,), N, u8 = srcs, self.N, dict(dtype=torch.uint8, device=self.device)
+        (s,), N = srcs, self.N
         reg, d, dd = shape.banks["conv"]                          # the valid convolution on the whole input
         ld = L.LearnedDesc(N, s.H, s.W, s.C, node.c_out, node.k, node.bc_x, node.bc_y, self.mc_dtype, node.sym_h)
         if L.call("mc_learned_validate", C.byref(ld)) != 0 or L.call("mc_conv_tiles", C.byref(d)) <= 0:
@@ -812,53 +1010,52 @@ class Engine:
                 fd = d
         coutp = ((node.c_out + 7) // 8) * 8
         tiles = min(64, o.H)
-        need_dgrad = s.requires_grad
-        e = dict(node=node, ldesc=ld, desc=d, fdesc=fd, ddesc=dd, fy=fy, fx=fx, mh=mh, mw=mw, tiles=tiles, coutp=coutp,
-                 Y=cb8(node.c_out, o.H, o.W), R=None if fd is not d else cb8(node.c_out, mh, mw), dR=cb8g(node.c_out, mh, mw),
-                 part=torch.empty((N, tiles, coutp, 2), **f32), need_dgrad=need_dgrad,
-                 dxl=cb8g(s.C, s.H, s.W) if need_dgrad else None,
-                 bank=torch.empty(L.call("mc_packed_weight_bytes", C.byref(fd), 0), **u8),
-                 dbank=torch.empty(L.call("mc_packed_weight_bytes", C.byref(d), 1), **u8) if need_dgrad else None,
-                 wpart=torch.empty(L.call("mc_wgrad_partial_bytes", C.byref(d)), **u8),
-                 lbank=torch.empty(L.call("mc_learned_bank_bytes", C.byref(ld), 0), **u8),
-                 ldbank=torch.empty(L.call("mc_learned_bank_bytes", C.byref(ld), 1), **u8) if need_dgrad else None,
-                 lws_bytes=L.call("mc_learned_wgrad_workspace_bytes", C.byref(ld)))
-        o.buf = cb8(node.c_out, o.H, o.W) if node.post != L.POST_NONE else e["Y"]
-        if node.post == L.POST_GN_ACT:
-            self._plan_gn(e, node, o, f32)
+        dg = s.requires_grad
+        e = LearnedPlan(node=node, route=route, ldesc=ld, desc=d, fdesc=fd, ddesc=dd, fy=fy, fx=fx, mh=mh, mw=mw, tiles=tiles,
+                        coutp=coutp, Y=self._cb8(node.c_out, o.H, o.W), R=None if fd is not d else self._cb8(node.c_out, mh, mw),
+                        dR=self._cb8(node.c_out, mh, mw, grad=True), part=self._f32(N, tiles, coutp, 2), need_dgrad=dg,
+                        dxl=self._cb8(s.C, s.H, s.W, grad=True) if dg else None,
+                        bank=self._u8(L.call("mc_packed_weight_bytes", C.byref(fd), 0)),
+                        dbank=self._u8(L.call("mc_packed_weight_bytes", C.byref(d), 1)) if dg else None,
+                        wpart=self._u8(L.call("mc_wgrad_partial_bytes", C.byref(d))),
+                        lbank=self._u8(L.call("mc_learned_bank_bytes", C.byref(ld), 0)),
+                        ldbank=self._u8(L.call("mc_learned_bank_bytes", C.byref(ld), 1)) if dg else None,
+                        lws_bytes=L.call("mc_learned_wgrad_workspace_bytes", C.byref(ld)), **self._plan_gn(node, o, route, coutp))
         return e
 
-    def _learned_forward(self, e, src, params, need_part, st):
-        node, N = e["node"], self.N
+    def _fwd_learned(self, e, params, st):
+        node, N, src = e.node, self.N, self.T[e.node.srcs[0]]
         bias = self._param(params, node.name + "learnable_bias")
-        o_h, o_w = e["Y"].shape[2], e["Y"].shape[3]
-        main = e["Y"] if e["R"] is None else e["R"]
-        L.call("mc_conv2d", C.byref(e["fdesc"]), L.ptr(src.buf), None, L.ptr(e["bank"]), L.ptr(bias), L.ptr(main), None, None, st)
-        if e["R"] is not None:
-            L.call("mc_rect_copy", L.ptr(e["R"]), e["mh"], e["mw"], 0, 0, L.ptr(e["Y"]), o_h, o_w, e["fy"], e["fx"], e["mh"], e["mw"],
+        o_h, o_w = e.Y.shape[2], e.Y.shape[3]
+        main = e.Y if e.R is None else e.R
+        L.call("mc_conv2d", C.byref(e.fdesc), L.ptr(src.buf), None, L.ptr(e.bank), L.ptr(bias), L.ptr(main), None, None, st)
+        if e.R is not None:
+            L.call("mc_rect_copy", L.ptr(e.R), e.mh, e.mw, 0, 0, L.ptr(e.Y), o_h, o_w, e.fy, e.fx, e.mh, e.mw,
                    N, node.c_out, 0, self.mc_dtype, st)
-        L.call("mc_learned_frame_fwd", C.byref(e["ldesc"]), L.ptr(src.buf), L.ptr(e["lbank"]), L.ptr(bias), L.ptr(e["Y"]), st)
-        if need_part:
-            L.call("mc_gn_partials", L.ptr(e["Y"]), N, node.c_out, o_h, o_w, self.mc_dtype, e["tiles"], L.ptr(e["part"]), st)
+        L.call("mc_learned_frame_fwd", C.byref(e.ldesc), L.ptr(src.buf), L.ptr(e.lbank), L.ptr(bias), L.ptr(e.Y), st)
+        if e.route.need_part:
+            L.call("mc_gn_partials", L.ptr(e.Y), N, node.c_out, o_h, o_w, self.mc_dtype, e.tiles, L.ptr(e.part), st)
+        self._fwd_gn(e, params, st)
 
-    def _learned_backward(self, e, src, dY, params, grads, st):
-        """The main bank's filter gradient joins the batched combine at the end of backward (e["wpart"]); its input gradient
+    def _bwd_learned(self, e, bk):
+        """The main bank's filter gradient joins the batched combine at the end of backward (e.wpart); its input gradient
         initialises dxl, the frame launch adds the eight border banks' to the border bands of dxl."""
-        node, N = e["node"], self.N
-        o_h, o_w = e["Y"].shape[2], e["Y"].shape[3]
-        L.call("mc_rect_copy", L.ptr(dY), o_h, o_w, e["fy"], e["fx"], L.ptr(e["dR"]), e["mh"], e["mw"], 0, 0, e["mh"], e["mw"], N,
+        self._bwd_gn(e, bk)
+        node, N, src, dY, grads, st = e.node, self.N, self.T[e.node.srcs[0]], self.dY, bk.grads, bk.st
+        o_h, o_w = e.Y.shape[2], e.Y.shape[3]
+        L.call("mc_rect_copy", L.ptr(dY), o_h, o_w, e.fy, e.fx, L.ptr(e.dR), e.mh, e.mw, 0, 0, e.mh, e.mw, N,
                node.c_out, 0, self.mc_gdtype, st)
-        L.call("mc_conv2d_wgrad", C.byref(e["desc"]), L.ptr(src.buf), None, L.ptr(e["dR"]), L.ptr(e["wpart"]), st)
+        L.call("mc_conv2d_wgrad", C.byref(e.desc), L.ptr(src.buf), None, L.ptr(e.dR), L.ptr(e.wpart), st)
         dws = (C.c_void_p * 8)(*[L.ptr(grads[node.name + b + ".weight"]) for b in L.LEARNED_FRAME_BANKS])
-        L.call("mc_learned_frame_wgrad", C.byref(e["ldesc"]), L.ptr(src.buf), L.ptr(dY), L.ptr(self.lws), dws,
+        L.call("mc_learned_frame_wgrad", C.byref(e.ldesc), L.ptr(src.buf), L.ptr(dY), L.ptr(self.lws), dws,
                L.ptr(grads[node.name + "learnable_bias"]), st)
-        if e["need_dgrad"]:
-            L.call("mc_conv2d", C.byref(e["ddesc"]), L.ptr(e["dR"]), None, L.ptr(e["dbank"]), None, L.ptr(e["dxl"]), None, None, st)
-            L.call("mc_learned_frame_dgrad", C.byref(e["ldesc"]), L.ptr(dY), L.ptr(e["ldbank"]), L.ptr(e["dxl"]), st)
-            src.gsrcs.append(L.GradSrc(L.ptr(e["dxl"]), L.GSRC_PLAIN, 0, 0, 1, src.H, src.W))
+        if e.need_dgrad:
+            L.call("mc_conv2d", C.byref(e.ddesc), L.ptr(e.dR), None, L.ptr(e.dbank), None, L.ptr(e.dxl), None, None, st)
+            L.call("mc_learned_frame_dgrad", C.byref(e.ldesc), L.ptr(dY), L.ptr(e.ldbank), L.ptr(e.dxl), st)
+            bk.plain(node.srcs[0], e.dxl, src)
 
     # -------------------------------------------------------------- spectral layers (SpectralConv2d)
-    def _plan_spectral(self, node, shape, srcs, o, cb8, cb8g, f32):
+    def _plan_spectral(self, node, shape, route, srcs, o):
         """A truncated DFT (csrc/spectral.hip): analysis of the materialised input, channel mixing in mode space, synthesis into
         the raw output Y with the GroupNorm partials.  The GroupNorm / activation / pooling launches after it are the generic
         ones; its input gradient is the input-sized buffer dxl, as for a learned-padding layer."""
@@ -868,51 +1065,41 @@ class Engine:
             raise L.MantleHipError(f"unsupported spectral layer {node.name}: input {s.H}x{s.W}")
         cinp, coutp = ((s.C + 7) // 8) * 8, ((node.c_out + 7) // 8) * 8
         cmax = max(cinp, coutp)
-        need_dgrad = s.requires_grad
-        e = dict(node=node, tiles=slots, coutp=coutp, Y=cb8(node.c_out, o.H, o.W), part=torch.empty((N, slots, coutp, 2), **f32),
-                 tabs=self._spectral_table(s.H, s.W), need_dgrad=need_dgrad,
-                 apart=torch.empty((N, slots, cmax, 32, 2), **f32),      # per-slot mode sums of the input / of dY
-                 xhat=torch.empty((N, cinp, 32, 2), **f32),              # modes of the input, kept for the backward pass
-                 mcoef=torch.empty((N, cmax, 32, 2), **f32),             # coefficients of the output / of the input gradient
-                 gbuf=torch.empty((N, coutp, 32, 2), **f32),
-                 dxl=cb8g(s.C, s.H, s.W) if need_dgrad else None)
-        o.buf = cb8(node.c_out, o.H, o.W) if node.post != L.POST_NONE else e["Y"]
-        if node.post == L.POST_GN_ACT:
-            self._plan_gn(e, node, o, f32)
+        e = SpectralPlan(node=node, route=route, tiles=slots, coutp=coutp, Y=self._cb8(node.c_out, o.H, o.W),
+                         part=self._f32(N, slots, coutp, 2), tabs=self._table(spectral_tables, s.H, s.W), need_dgrad=s.requires_grad,
+                         apart=self._f32(N, slots, cmax, 32, 2), xhat=self._f32(N, cinp, 32, 2), mcoef=self._f32(N, cmax, 32, 2),
+                         gbuf=self._f32(N, coutp, 32, 2), dxl=self._cb8(s.C, s.H, s.W, grad=True) if s.requires_grad else None,
+                         **self._plan_gn(node, o, route, coutp))
         return e
 
-    def _spectral_table(self, H, W):
-        key = ("spectral", H, W)
-        if key not in self._tables:
-            self._tables[key] = tuple(torch.from_numpy(a).to(self.device) for a in spectral_tables(H, W))
-        return self._tables[key]
-
-    def _spectral_forward(self, e, src, params, need_part, st):
-        node, N = e["node"], self.N
+    def _fwd_spectral(self, e, params, st):
+        node, N, src = e.node, self.N, self.T[e.node.srcs[0]]
         w1, w2 = self._param(params, node.name + "weights1"), self._param(params, node.name + "weights2")
-        rowtw, coltw = e["tabs"]
+        rowtw, coltw = e.tabs
         L.call("mc_spectral_analyze", L.ptr(src.buf), N, src.C, src.H, src.W, self.mc_dtype, L.ptr(rowtw), L.ptr(coltw),
-               L.ptr(e["apart"]), st)
-        L.call("mc_spectral_mix_fwd", L.ptr(e["apart"]), N, e["tiles"], src.C, node.c_out, src.H * src.W, L.ptr(w1), L.ptr(w2),
-               L.ptr(e["xhat"]), L.ptr(e["mcoef"]), st)
-        L.call("mc_spectral_synthesize", L.ptr(e["mcoef"]), N, node.c_out, src.H, src.W, self.mc_dtype, L.ptr(rowtw), L.ptr(coltw),
-               L.ptr(e["Y"]), L.ptr(e["part"]) if need_part else None, st)
+               L.ptr(e.apart), st)
+        L.call("mc_spectral_mix_fwd", L.ptr(e.apart), N, e.tiles, src.C, node.c_out, src.H * src.W, L.ptr(w1), L.ptr(w2),
+               L.ptr(e.xhat), L.ptr(e.mcoef), st)
+        L.call("mc_spectral_synthesize", L.ptr(e.mcoef), N, node.c_out, src.H, src.W, self.mc_dtype, L.ptr(rowtw), L.ptr(coltw),
+               L.ptr(e.Y), L.ptr(e.part) if e.route.need_part else None, st)
+        self._fwd_gn(e, params, st)
 
-    def _spectral_backward(self, e, src, dY, params, grads, st):
+    def _bwd_spectral(self, e, bk):
         """dY -> its modes -> the two weight gradients (accumulated, samples in order) and the coefficients of the input
         gradient -> dxl."""
-        node, N = e["node"], self.N
-        w1, w2 = self._param(params, node.name + "weights1"), self._param(params, node.name + "weights2")
-        rowtw, coltw = e["tabs"]
+        self._bwd_gn(e, bk)
+        node, N, src, dY, grads, st = e.node, self.N, self.T[e.node.srcs[0]], self.dY, bk.grads, bk.st
+        w1, w2 = self._param(bk.params, node.name + "weights1"), self._param(bk.params, node.name + "weights2")
+        rowtw, coltw = e.tabs
         L.call("mc_spectral_analyze", L.ptr(dY), N, node.c_out, src.H, src.W, self.mc_gdtype, L.ptr(rowtw), L.ptr(coltw),
-               L.ptr(e["apart"]), st)
-        L.call("mc_spectral_mix_bwd", L.ptr(e["apart"]), N, e["tiles"], src.C, node.c_out, src.H * src.W, L.ptr(w1), L.ptr(w2),
-               L.ptr(e["xhat"]), L.ptr(e["gbuf"]), L.ptr(grads[node.name + "weights1"]), L.ptr(grads[node.name + "weights2"]),
-               L.ptr(e["mcoef"]) if e["need_dgrad"] else None, st)
-        if e["need_dgrad"]:
-            L.call("mc_spectral_synthesize", L.ptr(e["mcoef"]), N, src.C, src.H, src.W, self.mc_gdtype, L.ptr(rowtw), L.ptr(coltw),
-                   L.ptr(e["dxl"]), None, st)
-            src.gsrcs.append(L.GradSrc(L.ptr(e["dxl"]), L.GSRC_PLAIN, 0, 0, 1, src.H, src.W))
+               L.ptr(e.apart), st)
+        L.call("mc_spectral_mix_bwd", L.ptr(e.apart), N, e.tiles, src.C, node.c_out, src.H * src.W, L.ptr(w1), L.ptr(w2),
+               L.ptr(e.xhat), L.ptr(e.gbuf), L.ptr(grads[node.name + "weights1"]), L.ptr(grads[node.name + "weights2"]),
+               L.ptr(e.mcoef) if e.need_dgrad else None, st)
+        if e.need_dgrad:
+            L.call("mc_spectral_synthesize", L.ptr(e.mcoef), N, src.C, src.H, src.W, self.mc_gdtype, L.ptr(rowtw), L.ptr(coltw),
+                   L.ptr(e.dxl), None, st)
+            bk.plain(node.srcs[0], e.dxl, src)
 
     def input_grad(self):
         """input_grad_cb8() as an NCHW f32 tensor (what the autograd bridge returns for the input)."""
@@ -924,15 +1111,15 @@ class Engine:
     def input_grad_cb8(self):
         """d(loss)/d(input) of a graph built with input_grad=True, as backward left it: CB8 [N][C8][H][W][8] in the gradient
         type (the first node must be a learned-padding or spectral layer reading the input)."""
-        e = self.plan[0]
-        if not self.g.input_grad or not e["node"].kind == "conv" or e.get("dxl") is None:
+        if not self.g.input_grad or getattr(self.plan[0], "dxl", None) is None:
             raise RuntimeError("this graph produces no input gradient")
-        return e["dxl"]
+        return self.plan[0].dxl
 
-    def _table(self, n_in, n_out):
-        key = (n_in, n_out)
+    def _table(self, build, *size):
+        """The host tables build(*size) (bicubic_tables, spectral_tables) as device tensors, built once per size."""
+        key = (build, *size)
         if key not in self._tables:
-            self._tables[key] = tuple(torch.from_numpy(a).to(self.device) for a in bicubic_tables(n_in, n_out))
+            self._tables[key] = tuple(torch.from_numpy(a).to(self.device) for a in build(*size))
         return self._tables[key]
 
     # -------------------------------------------------------------- forward
@@ -940,7 +1127,7 @@ class Engine:
         """The last convolution's output as the forward pass left it, for consumers that read the CB8 layout themselves
         (StokesLoss.evaluate(cb8=...)): (buffer [N][C8][H][W + 2 crop][8] f32, per-(sample, channel) spatial means or None,
         crop, (N, C, H, W)); None when the head does not end in an f32 tensor."""
-        fo = self.T[self.plan[-1]["node"].out]
+        fo = self.T[self.plan[-1].node.out]
         if fo.buf is None or fo.buf.dtype != torch.float32 or fo.C != self.g.c_out:
             return None
         return fo.buf, (self.chan_mean if self.g.subtract_mean else None), self.g.crop_w, (self.N, self.g.c_out, self.out_h, self.out_w)
@@ -962,7 +1149,6 @@ class Engine:
         self.configure(N, H, W, x.device)
         st = L.stream()
         g, T = self.g, self.T
-        act = L.ACTS[g.act]
         self._drop_on = bool(drop) and self.has_drop
         if self._drop_on:
             L.call("mc_dropout_advance", L.ptr(self.drop_state), st)
@@ -970,77 +1156,8 @@ class Engine:
                L.ptr(T[0].buf), st)
         self._pack_all_banks(params, st)
         for e in self.plan:
-            node = e["node"]
-            if node.kind == "pool":
-                s, o = T[node.src], T[node.out]
-                L.call("mc_avgpool_fwd", L.ptr(s.buf), N, s.C, s.H, s.W, node.f, self.mc_dtype, L.ptr(o.buf), st)
-                continue
-            if node.kind == "cat":
-                srcs = [T[i] for i in node.srcs]
-                o = T[node.out]
-                ptrs = (C.c_void_p * len(srcs))(*[L.ptr(t.buf) for t in srcs])
-                cs = (C.c_int32 * len(srcs))(*[t.C for t in srcs])
-                L.call("mc_concat_cb8", ptrs, cs, len(srcs), N, o.H, o.W, self.mc_dtype, L.ptr(o.buf), st)
-                continue
-            if node.kind == "up":
-                s, o = T[node.src], T[node.out]
-                (iy, wy, *_), (ix, wx, *_) = e["tabs"]
-                if s.fused:      # the producer's GroupNorm + activation are applied while the input window is staged
-                    L.call("mc_bicubic_fwd_act", L.ptr(s.raw), L.ptr(s.coef), s.act, N, s.C, s.H, s.W, o.H, o.W, L.ptr(iy),
-                           L.ptr(wy), L.ptr(ix), L.ptr(wx), self.mc_dtype, L.ptr(o.buf), st)
-                else:
-                    L.call("mc_bicubic_fwd", L.ptr(s.buf), N, s.C, s.H, s.W, o.H, o.W, L.ptr(iy), L.ptr(wy), L.ptr(ix),
-                           L.ptr(wx), self.mc_dtype, L.ptr(o.buf), st)
-                continue
-            d = e.get("desc")
-            if not node.learned and not node.spectral:
-                w = self._param(params, node.name + "weight")
-                b = self._param(params, node.name + "bias")
-            srcs = [T[i] for i in node.srcs]
-            o = T[node.out]
-            final = node.post == L.POST_NONE
-            need_part = node.post == L.POST_GN_ACT or (final and g.subtract_mean)
-            gamma = self._param(params, node.gn_name + "weight") if node.gn_name else None
-            beta = self._param(params, node.gn_name + "bias") if node.gn_name else None
-            if node.learned:
-                self._learned_forward(e, srcs[0], params, need_part, st)
-            elif node.spectral:
-                self._spectral_forward(e, srcs[0], params, need_part, st)
-            else:
-                self._probe_begin()
-                x0, x1, pro = self._sources(srcs)
-                L.call("mc_conv2d_fused", C.byref(d), x0, x1, pro, L.ptr(e["bank"]), L.ptr(b), L.ptr(e["Y"]), None,
-                       L.ptr(e["part"]) if need_part else None, None, st)
-                self._probe_end(d, "fwd " + node.name)
-            small = (node.post == L.POST_GN_ACT and "pc" in e and not o.fused and node.pool in (1, 2)
-                     and not node.learned and not node.spectral and (self.fuse == 0 or self.fuse_dz_rr) and "dz_blocks" not in e)
-            if small:
-                # statistics + activation (+ pooling) of a small layer in one launch
-                pooled = T[node.pooled].buf if node.pool > 1 else None
-                dr = self._drop_desc(node)
-                L.call("mc_gn_act_fwd_small" + ("_drop" if dr else ""), L.ptr(e["Y"]), L.ptr(e["part"]), e["tiles"], N, node.c_out,
-                       o.H, o.W, node.groups, 1e-5, L.ptr(gamma), L.ptr(beta), act, node.pool, self.mc_dtype, L.ptr(e["stats"]),
-                       L.ptr(o.buf), L.ptr(pooled), *((C.byref(dr),) if dr else ()), st)
-                continue
-            if node.post == L.POST_GN_ACT:
-                # (mean, rstd) per (sample, group) + the (scale, shift, mean, rstd) table consumers normalise on load with
-                L.call("mc_gn_finalize_coef", L.ptr(e["part"]), N, e["tiles"], node.c_out, node.groups, o.H * o.W, 1e-5,
-                       L.ptr(gamma), L.ptr(beta), L.ptr(e["stats"]), L.ptr(e.get("coef")), st)
-            if o.fused:
-                if node.pool > 1:      # only the pooled tensor is materialised
-                    L.call("mc_gn_act_fwd", L.ptr(e["Y"]), N, node.c_out, o.H, o.W, node.groups, L.ptr(e.get("stats")),
-                           L.ptr(gamma), L.ptr(beta), node.post, act, node.pool, self.mc_dtype, None,
-                           L.ptr(T[node.pooled].buf), st)
-            elif not final:
-                pooled = T[node.pooled].buf if node.pool > 1 else None
-                dr = self._drop_desc(node)
-                L.call("mc_gn_act_fwd" + ("_drop" if dr else ""), L.ptr(e["Y"]), N, node.c_out, o.H, o.W, node.groups,
-                       L.ptr(e.get("stats")), L.ptr(gamma), L.ptr(beta), node.post, act, node.pool, self.mc_dtype,
-                       L.ptr(o.buf), L.ptr(pooled), *((C.byref(dr),) if dr else ()), st)
-            elif g.subtract_mean:
-                L.call("mc_gn_finalize", L.ptr(e["part"]), N, e["tiles"], node.c_out, 1, o.H * o.W, 1e-5, None,
-                       L.ptr(self.chan_mean), st)
-        fo = T[self.plan[-1]["node"].out]
+            getattr(self, "_fwd_" + e.op)(e, params, st)
+        fo = T[self.plan[-1].node.out]
         if not unpack and self.output_cb8() is not None:      # the caller reads output_cb8() (no NCHW copy of the output)
             return None
         if out is None:
@@ -1051,6 +1168,62 @@ class Engine:
         L.call("mc_unpack_nchw", L.ptr(fo.buf), N, fo.C, fo.H, fo.W, g.crop_w, L.ptr(self.chan_mean), out_dt,
                L.ptr(out), st)
         return out
+
+    def _fwd_pool(self, e, params, st):
+        s, o = self.T[e.node.src], self.T[e.node.out]
+        L.call("mc_avgpool_fwd", L.ptr(s.buf), self.N, s.C, s.H, s.W, e.node.f, self.mc_dtype, L.ptr(o.buf), st)
+
+    def _fwd_cat(self, e, params, st):
+        srcs, o = [self.T[i] for i in e.node.srcs], self.T[e.node.out]
+        ptrs, cs = _columns([(L.ptr(t.buf), t.C) for t in srcs], C.c_void_p, C.c_int32)
+        L.call("mc_concat_cb8", ptrs, cs, len(srcs), self.N, o.H, o.W, self.mc_dtype, L.ptr(o.buf), st)
+
+    def _fwd_up(self, e, params, st):
+        s, o, N = self.T[e.node.src], self.T[e.node.out], self.N
+        (iy, wy, *_), (ix, wx, *_) = e.tabs
+        # a fused source: the producer's GroupNorm + activation are applied while the input window is staged
+        sfx, src = ("_act", (L.ptr(s.raw), L.ptr(s.coef), s.act)) if s.fused else ("", (L.ptr(s.buf),))
+        L.call("mc_bicubic_fwd" + sfx, *src, N, s.C, s.H, s.W, o.H, o.W, L.ptr(iy), L.ptr(wy), L.ptr(ix), L.ptr(wx),
+               self.mc_dtype, L.ptr(o.buf), st)
+
+    def _fwd_conv(self, e, params, st):
+        node, d = e.node, e.desc
+        b = self._param(params, node.name + "bias")
+        self._probe_begin()
+        x0, x1, pro = self._sources([self.T[i] for i in node.srcs])
+        L.call("mc_conv2d_fused", C.byref(d), x0, x1, pro, L.ptr(e.bank), L.ptr(b), L.ptr(e.Y), None,
+               L.ptr(e.part) if e.route.need_part else None, None, st)
+        self._probe_end(d, "fwd " + node.name)
+        self._fwd_gn(e, params, st)
+
+    def _fwd_gn(self, e, params, st):
+        """What follows the conv launch of any kind of conv layer: the route's GroupNorm / activation / pooling form."""
+        node, N, o, form = e.node, self.N, self.T[e.node.out], e.route.gn_fwd
+        if form is GnFwd.NONE:
+            return
+        if form is GnFwd.MEANS:
+            L.call("mc_gn_finalize", L.ptr(e.part), N, e.tiles, node.c_out, 1, o.H * o.W, 1e-5, None, L.ptr(self.chan_mean), st)
+            return
+        gamma, beta = self._gn_params(node, params)
+        act, pooled = L.ACTS[self.g.act], (self.T[node.pooled].buf if node.pool > 1 else None)
+        sfx, dra = self._drop(node)
+        if form is GnFwd.SMALL:
+            L.call("mc_gn_act_fwd_small" + sfx, L.ptr(e.Y), L.ptr(e.part), e.tiles, N, node.c_out, o.H, o.W, node.groups, 1e-5,
+                   L.ptr(gamma), L.ptr(beta), act, node.pool, self.mc_dtype, L.ptr(e.stats), L.ptr(o.buf), L.ptr(pooled), *dra, st)
+            return
+        if node.post == L.POST_GN_ACT:
+            # (mean, rstd) per (sample, group) + the (scale, shift, mean, rstd) table consumers normalise on load with
+            L.call("mc_gn_finalize_coef", L.ptr(e.part), N, e.tiles, node.c_out, node.groups, o.H * o.W, 1e-5,
+                   L.ptr(gamma), L.ptr(beta), L.ptr(e.stats), L.ptr(getattr(e, "coef", None)), st)
+        if form is GnFwd.APPLY or node.pool > 1:      # FUSED: only the pooled tensor is materialised (o.buf is None)
+            L.call("mc_gn_act_fwd" + sfx, L.ptr(e.Y), N, node.c_out, o.H, o.W, node.groups, L.ptr(e.stats), L.ptr(gamma),
+                   L.ptr(beta), node.post, act, node.pool, self.mc_dtype, L.ptr(o.buf), L.ptr(pooled), *dra, st)
+
+    def _gn_params(self, node, params):
+        """(gamma, beta) of the node's GroupNorm, (None, None) without one."""
+        if not node.gn_name:
+            return None, None
+        return self._param(params, node.gn_name + "weight"), self._param(params, node.gn_name + "bias")
 
     @staticmethod
     def _sources(srcs):
@@ -1079,14 +1252,11 @@ class Engine:
         (StokesLoss.gradient_sums()): the spatial means of gout are then taken from them instead of a pass over gout."""
         L.require_cuda(gout, "output gradient")
         gout = gout.contiguous().float()
-        g, T, N = self.g, self.T, self.N
+        g, N = self.g, self.N
         st = L.stream()
-        act = L.ACTS[g.act]
-        for t in T.values():
-            t.gsrcs = []
-        dY = self.dY                                         # every layer's output gradient (see configure)
-        gp_jobs = []                                         # GroupNorm parameter gradients of the one-launch layers
-        fo = T[self.plan[-1]["node"].out]
+        bk = _Backward(params, grads, st)
+        last = self.plan[-1].node
+        fo = self.T[last.out]
         mean = None
         if g.subtract_mean:
             if gsum is not None and g.c_out <= 4 and tuple(gsum[0].shape) == (N, gsum[1], 4):
@@ -1095,219 +1265,187 @@ class Engine:
                 L.call("mc_sum_hw", L.ptr(gout), N * g.c_out, self.out_h * self.out_w, 1.0 / (fo.H * fo.W),
                        L.ptr(self.gmean), st)
             mean = self.gmean
-        gdst = dY if self.final_plain else self.dOut
+        gdst = self.dY if self.final_plain else self.dOut        # self.dY: every layer's output gradient (see configure)
         L.call("mc_pack_grad_nchw", L.ptr(gout), N, g.c_out, fo.H, fo.W, g.crop_w, L.ptr(mean), self.mc_gdtype,
                L.ptr(gdst), st)
         if not self.final_plain:
-            fo.gsrcs.append(L.GradSrc(L.ptr(self.dOut), L.GSRC_PLAIN, 0, 0, 1, fo.H, fo.W))
+            bk.plain(last.out, self.dOut, fo)
         for e in reversed(self.plan):
-            node = e["node"]
-            if node.kind == "cat":
-                # the gradient of the concatenated tensor is one buffer; an aligned operand reads its channel-block slice,
-                # an unaligned one its own buffer gathered from it (see configure)
-                o = T[node.out]
-                assert len(o.gsrcs) == 1, "a concatenated tensor feeds exactly one conv"
-                q = o.gsrcs[0]
-                c8_total = (o.C + 7) // 8
-                off = 0
-                for i in node.srcs:
-                    t = T[i]
-                    if i in e["gather"]:
-                        c_off, buf = e["gather"][i]
-                        L.call("mc_cat_grad_gather", C.byref(q), o.C, c_off, t.C, N, t.H, t.W, self.mc_gdtype, L.ptr(buf), st)
-                        t.gsrcs.append(L.GradSrc(L.ptr(buf), L.GSRC_PLAIN, 0, 0, 1, t.H, t.W))
-                    elif t.requires_grad:
-                        t.gsrcs.append(L.GradSrc(q.ptr, q.kind, q.pad, q.pad_mode, q.pool, q.hs, q.ws, c8_total, off // 8))
-                    off += t.C
-                continue
-            if node.kind == "pool":
-                # d(src) += AvgPool adjoint of d(out); d(out) has one source (the conv it feeds) or two (+ the next pooling level)
-                s, o = T[node.src], T[node.out]
-                assert 1 <= len(o.gsrcs) <= 2
-                if not s.requires_grad:
-                    continue
-                q = o.gsrcs[0]
-                if len(o.gsrcs) == 1 and q.kind == L.GSRC_PADFOLD and q.c8_total == 0:
-                    s.gsrcs.append(L.GradSrc(q.ptr, L.GSRC_PADFOLD_POOL, q.pad, q.pad_mode, node.f, o.H, o.W))
-                else:
-                    g1 = C.byref(o.gsrcs[1]) if len(o.gsrcs) > 1 else None
-                    L.call("mc_gsrc_sum", C.byref(q), g1, N, o.C, o.H, o.W, self.mc_gdtype, L.ptr(e["dsum"]), st)
-                    s.gsrcs.append(L.GradSrc(L.ptr(e["dsum"]), L.GSRC_PLAIN_POOL, 0, 0, node.f, o.H, o.W))
-                continue
-            if node.kind == "up":
-                s, o = T[node.src], T[node.out]
-                assert len(o.gsrcs) == 1, "an upsampled tensor feeds exactly one conv"
-                (iy, wy, tys, tyj, tyw), (_, _, txs, txj, txw) = e["tabs"]
-                if "bws" not in e and e["maxtaps"][1] <= 12:
-                    L.call("mc_bicubic_bwd_walk", C.byref(o.gsrcs[0]), N, s.C, s.H, s.W, o.H, o.W, L.ptr(iy), L.ptr(wy), L.ptr(tys),
-                           L.ptr(tyj), L.ptr(txs), L.ptr(txj), L.ptr(txw), e["maxtaps"][1], self.mc_gdtype, L.ptr(e["dsrc"]), st)
-                elif "bws" in e:
-                    L.call("mc_bicubic_bwd_separable", C.byref(o.gsrcs[0]), N, s.C, s.H, s.W, o.H, o.W, L.ptr(tys), L.ptr(tyj),
-                           L.ptr(tyw), L.ptr(txs), L.ptr(txj), L.ptr(txw), self.mc_gdtype, L.ptr(e["bws"]), L.ptr(e["dsrc"]), st)
-                else:
-                    L.call("mc_bicubic_bwd_taps", C.byref(o.gsrcs[0]), N, s.C, s.H, s.W, o.H, o.W, L.ptr(tys), L.ptr(tyj),
-                           L.ptr(tyw), L.ptr(txs), L.ptr(txj), L.ptr(txw), e["maxtaps"][0], e["maxtaps"][1], self.mc_gdtype,
-                           L.ptr(e["dsrc"]), st)
-                s.gsrcs.append(L.GradSrc(L.ptr(e["dsrc"]), L.GSRC_PLAIN, 0, 0, 1, s.H, s.W))
-                continue
-            d = e.get("desc")
-            o = T[node.out]
-            srcs = [T[i] for i in node.srcs]
-            wdz = False
-            if node.post != L.POST_NONE and "dz" in e:
-                # dz = dA * act'(z) and its partial sums were produced by the consumer's input-gradient launch
-                assert not o.gsrcs, f"{node.name}: fused dz and separate gradient sources"
-                wdz = "dz_coef" in e                     # dY is formed by the filter-gradient launch below
-                if node.post == L.POST_GN_ACT:
-                    gamma = self._param(params, node.gn_name + "weight")
-                    sfx, tab = ("_dz", (L.ptr(e["coef"]), L.ptr(e["dz_coef"]))) if wdz else ("", ())
-                    if "dz_pc" in e:
-                        # many slots per sample: one block per (group, sample); dgamma / dbeta join the batched launch below
-                        L.call("mc_gn_act_bwd_finalize_n" + sfx, L.ptr(e["dz_part"]), N, e["dz_blocks"], node.c_out, node.groups,
-                               o.H * o.W, L.ptr(gamma), L.ptr(e["m12"]), L.ptr(e["dz_pc"]), *tab, st)
-                        gp_jobs.append((L.ptr(e["dz_pc"]), node.c_out, L.ptr(grads[node.gn_name + "weight"]),
-                                        L.ptr(grads[node.gn_name + "bias"])))
-                    else:
-                        L.call("mc_gn_act_bwd_finalize" + sfx, L.ptr(e["dz_part"]), N, e["dz_blocks"], node.c_out, node.groups,
-                               o.H * o.W, L.ptr(gamma), L.ptr(e["m12"]), L.ptr(grads[node.gn_name + "weight"]),
-                               L.ptr(grads[node.gn_name + "bias"]), *tab, st)
-                if wdz:
-                    x0, x1, _ = self._sources(srcs)
-                    L.call("mc_conv2d_wgrad_dz", C.byref(d), x0, x1, C.byref(e["dz"]), L.ptr(e["Y"]), L.ptr(e["dz_coef"]),
-                           L.ptr(dY), L.ptr(e["wpart"]), st)
-                else:
-                    L.call("mc_gn_bwd_apply_dz", C.byref(e["dz"]), L.ptr(e["Y"]), N, node.c_out, o.H, o.W, max(node.groups, 1),
-                           L.ptr(e["coef"]) if node.post == L.POST_GN_ACT else None, L.ptr(e.get("m12")), self.mc_dtype,
-                           L.ptr(dY), st)
-                del e["dz"]
-            elif node.post != L.POST_NONE:
-                gs = list(o.gsrcs)
-                if node.pool > 1:
-                    p = T[node.pooled]
-                    for q in p.gsrcs:
-                        assert q.kind in (L.GSRC_PADFOLD, L.GSRC_PLAIN) and q.c8_total == 0, "a pooled tensor feeds exactly one conv"
-                        kind = L.GSRC_PADFOLD_POOL if q.kind == L.GSRC_PADFOLD else L.GSRC_PLAIN_POOL   # (PLAIN: learned-padding conv)
-                        gs.append(L.GradSrc(q.ptr, kind, q.pad, q.pad_mode, node.pool, p.H, p.W))
-                assert 1 <= len(gs) <= 2, f"{node.name}: {len(gs)} gradient sources"
-                g0 = C.byref(gs[0])
-                g1 = C.byref(gs[1]) if len(gs) > 1 else None
-                gamma = self._param(params, node.gn_name + "weight") if node.gn_name else None
-                beta = self._param(params, node.gn_name + "bias") if node.gn_name else None
-                dr = self._drop_desc(node)           # the forward's mask, regenerated from the same (seed, step, layer)
-                sfx, dra = ("_drop", (C.byref(dr),)) if dr else ("", ())
-                if node.post == L.POST_GN_ACT and "pc" in e:
-                    L.call("mc_gn_act_bwd_small" + sfx, L.ptr(e["Y"]), N, node.c_out, o.H, o.W, node.groups, L.ptr(e["stats"]),
-                           L.ptr(gamma), L.ptr(beta), act, self.mc_dtype, g0, g1, L.ptr(dY), L.ptr(e["pc"]), *dra, st)
-                    gp_jobs.append((L.ptr(e["pc"]), node.c_out, L.ptr(grads[node.gn_name + "weight"]),
-                                    L.ptr(grads[node.gn_name + "bias"])))
-                else:
-                    if node.post == L.POST_GN_ACT:
-                        L.call("mc_gn_act_bwd_reduce" + sfx, L.ptr(e["Y"]), N, node.c_out, o.H, o.W, node.groups,
-                               L.ptr(e["stats"]), L.ptr(gamma), L.ptr(beta), node.post, act, self.mc_dtype, g0, g1,
-                               L.ptr(e["gpart"]), *dra, st)
-                        L.call("mc_gn_act_bwd_finalize", L.ptr(e["gpart"]), N, e["gblocks"], node.c_out, node.groups,
-                               o.H * o.W, L.ptr(gamma), L.ptr(e["m12"]), L.ptr(grads[node.gn_name + "weight"]),
-                               L.ptr(grads[node.gn_name + "bias"]), st)
-                    L.call("mc_gn_act_bwd_apply" + sfx, L.ptr(e["Y"]), N, node.c_out, o.H, o.W, node.groups,
-                           L.ptr(e.get("stats")), L.ptr(e.get("m12")), L.ptr(gamma), L.ptr(beta), node.post, act,
-                           self.mc_dtype, g0, g1, L.ptr(dY), *dra, st)
-            if node.learned:
-                self._learned_backward(e, srcs[0], dY, params, grads, st)
-                continue
-            if node.spectral:
-                self._spectral_backward(e, srcs[0], dY, params, grads, st)
-                continue
-            if not wdz:
-                x0, x1, pro = self._sources(srcs)
-                L.call("mc_conv2d_wgrad_fused", C.byref(d), x0, x1, pro, L.ptr(dY), L.ptr(e["wpart"]), st)
-            if e["need_dgrad"]:
-                dxp = e["dxp"]
-                pe = e.get("epi")
-                if pe is not None:
-                    # the source's GroupNorm-backward reduction rides in this launch: dz and its partial sums instead of dA
-                    pn, s0 = pe["node"], srcs[0]
-                    coef = L.ptr(pe["coef"]) if pn.post == L.POST_GN_ACT else None
-                    epi = L.ConvEpilogue(L.ptr(pe["Y"]), coef, act, node.pad, self.mode, s0.H, s0.W, L.ptr(pe["dz_part"]),
-                                         pe["dz_blocks"], int(self.mc_dtype == L.MC_MIX16))
-                    self._probe_begin()
-                    L.call("mc_conv2d_fused", C.byref(e["ddesc"]), L.ptr(dY), None, None, L.ptr(e["dbank"]), None,
-                           L.ptr(dxp[0]), None, None, C.byref(epi), st)
-                    self._probe_end(e["ddesc"], "dgrad+dz " + node.name, extra_in=s0.C * s0.H * s0.W)
-                    L.call("mc_fold_padded_dz", L.ptr(dxp[0]), N, s0.C, s0.H, s0.W, node.pad, self.mode, self.mc_dtype,
-                           L.ptr(pe["Y"]), coef, act, L.ptr(pe["dz_part"]), pe["dz_blocks"], pe["dz_tiles"], st)
-                    pe["dz"] = L.GradSrc(L.ptr(dxp[0]), L.GSRC_PADFOLD, node.pad, self.mode, 1, s0.H, s0.W)
-                    continue
-                self._probe_begin()
-                L.call("mc_conv2d", C.byref(e["ddesc"]), L.ptr(dY), None, L.ptr(e["dbank"]), None, L.ptr(dxp[0]),
-                       L.ptr(dxp[1]) if len(dxp) > 1 else None, None, st)
-                self._probe_end(e["ddesc"], "dgrad " + node.name)
-                # adjoint of the padding: fold the halo onto the interior once, consumers read at an offset (the two outputs of
-                # a convolution over concatenated sources in one launch)
-                live = [(s, buf) for s, buf in zip(srcs, dxp) if s.requires_grad]
-                if len(live) == 2 and (live[0][0].H, live[0][0].W) == (live[1][0].H, live[1][0].W):
-                    L.call("mc_fold_padded2", L.ptr(live[0][1]), live[0][0].C, L.ptr(live[1][1]), live[1][0].C, N, live[0][0].H,
-                           live[0][0].W, node.pad, self.mode, self.mc_gdtype, st)
-                else:
-                    for s, buf in live:
-                        L.call("mc_fold_padded", L.ptr(buf), N, s.C, s.H, s.W, node.pad, self.mode, self.mc_gdtype, st)
-                for s, buf in live:
-                    s.gsrcs.append(L.GradSrc(L.ptr(buf), L.GSRC_PADFOLD, node.pad, self.mode, 1, s.H, s.W))
-        if gp_jobs:
-            n = len(gp_jobs)
-            L.call("mc_gn_param_grads_batched", (C.c_void_p * n)(*[j[0] for j in gp_jobs]), (C.c_int32 * n)(*([N] * n)),
-                   (C.c_int32 * n)(*[j[1] for j in gp_jobs]), (C.c_void_p * n)(*[j[2] for j in gp_jobs]),
-                   (C.c_void_p * n)(*[j[3] for j in gp_jobs]), n, st)
+            getattr(self, "_bwd_" + e.op)(e, bk)
+        if bk.gp_jobs:
+            L.call("mc_gn_param_grads_batched", *_columns(bk.gp_jobs, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p),
+                   len(bk.gp_jobs), st)
         # one launch combines every layer's partial slabs, folds mirrored filters and accumulates into the gradients
         # (a learned layer's main bank: its valid convolution; the shared bias takes its interior share here)
-        jobs = [(e["desc"], e["wpart"], e["node"].name + "weight", e["node"].name + "bias") for e in self.convs]
-        jobs += [(e["desc"], e["wpart"], e["node"].name + "conv.weight", e["node"].name + "learnable_bias") for e in self.learned]
-        n = len(jobs)
-        if n:
-            descs = (L.ConvDesc * n)(*[j[0] for j in jobs])
-            parts = (C.c_void_p * n)(*[L.ptr(j[1]) for j in jobs])
-            dws = (C.c_void_p * n)(*[L.ptr(grads[j[2]]) for j in jobs])
-            dbs = (C.c_void_p * n)(*[L.ptr(grads[j[3]]) for j in jobs])
-            L.call("mc_conv2d_wgrad_finalize_batched", descs, parts, dws, dbs, n, st)
+        jobs = [(e.desc, L.ptr(e.wpart), L.ptr(grads[e.node.name + w]), L.ptr(grads[e.node.name + b]))
+                for es, w, b in ((self.convs, "weight", "bias"), (self.learned, "conv.weight", "learnable_bias")) for e in es]
+        if jobs:
+            L.call("mc_conv2d_wgrad_finalize_batched", *_columns(jobs, L.ConvDesc, C.c_void_p, C.c_void_p, C.c_void_p), len(jobs), st)
+
+    def _bwd_cat(self, e, bk):
+        """The gradient of the concatenated tensor is one buffer; an aligned operand reads its channel-block slice, an
+        unaligned one its own buffer gathered from it (see _plan_cat)."""
+        node, T, N, o = e.node, self.T, self.N, self.T[e.node.out]
+        assert len(bk.srcs[node.out]) == 1, "a concatenated tensor feeds exactly one conv"
+        q = bk.srcs[node.out][0]
+        off = 0
+        for i in node.srcs:
+            t = T[i]
+            if i in e.gather:
+                c_off, buf = e.gather[i]
+                L.call("mc_cat_grad_gather", C.byref(q), o.C, c_off, t.C, N, t.H, t.W, self.mc_gdtype, L.ptr(buf), bk.st)
+                bk.plain(i, buf, t)
+            elif t.requires_grad:
+                bk.srcs[i].append(L.GradSrc(q.ptr, q.kind, q.pad, q.pad_mode, q.pool, q.hs, q.ws, (o.C + 7) // 8, off // 8))
+            off += t.C
+
+    def _bwd_pool(self, e, bk):
+        """d(src) += AvgPool adjoint of d(out); d(out) has one source (the conv it feeds) or two (+ the next pooling level)."""
+        node, s, o = e.node, self.T[e.node.src], self.T[e.node.out]
+        gs = bk.srcs[node.out]
+        assert 1 <= len(gs) <= 2
+        if not s.requires_grad:
+            return
+        q = gs[0]
+        if len(gs) == 1 and q.kind == L.GSRC_PADFOLD and q.c8_total == 0:
+            bk.srcs[node.src].append(L.GradSrc(q.ptr, L.GSRC_PADFOLD_POOL, q.pad, q.pad_mode, node.f, o.H, o.W))
+        else:
+            g1 = C.byref(gs[1]) if len(gs) > 1 else None
+            L.call("mc_gsrc_sum", C.byref(q), g1, self.N, o.C, o.H, o.W, self.mc_gdtype, L.ptr(e.dsum), bk.st)
+            bk.srcs[node.src].append(L.GradSrc(L.ptr(e.dsum), L.GSRC_PLAIN_POOL, 0, 0, node.f, o.H, o.W))
+
+    def _bwd_up(self, e, bk):
+        node, s, o, N, st = e.node, self.T[e.node.src], self.T[e.node.out], self.N, bk.st
+        assert len(bk.srcs[node.out]) == 1, "an upsampled tensor feeds exactly one conv"
+        (iy, wy, tys, tyj, tyw), (_, _, txs, txj, txw) = e.tabs
+        head, (my, mx) = (C.byref(bk.srcs[node.out][0]), N, s.C, s.H, s.W, o.H, o.W), e.route.maxtaps
+        taps = (L.ptr(tys), L.ptr(tyj), L.ptr(tyw), L.ptr(txs), L.ptr(txj), L.ptr(txw))
+        if e.route.bwd is UpBwd.WALK:
+            L.call("mc_bicubic_bwd_walk", *head, L.ptr(iy), L.ptr(wy), L.ptr(tys), L.ptr(tyj), L.ptr(txs), L.ptr(txj), L.ptr(txw),
+                   mx, self.mc_gdtype, L.ptr(e.dsrc), st)
+        elif e.route.bwd is UpBwd.SEPARABLE:
+            L.call("mc_bicubic_bwd_separable", *head, *taps, self.mc_gdtype, L.ptr(e.bws), L.ptr(e.dsrc), st)
+        else:
+            L.call("mc_bicubic_bwd_taps", *head, *taps, my, mx, self.mc_gdtype, L.ptr(e.dsrc), st)
+        bk.plain(node.src, e.dsrc, s)
+
+    def _bwd_gn(self, e, bk):
+        """dY of any kind of conv layer from the gradient of its activated output, in the route's form."""
+        node, N, o, form, dY, st = e.node, self.N, self.T[e.node.out], e.route.gn_bwd, self.dY, bk.st
+        if form is GnBwd.NONE:
+            return
+        gn, act = node.post == L.POST_GN_ACT, L.ACTS[self.g.act]
+        gamma, beta = self._gn_params(node, bk.params)
+        dgamma, dbeta = (L.ptr(bk.grads[node.gn_name + "weight"]), L.ptr(bk.grads[node.gn_name + "bias"])) if gn else (None, None)
+        if form in DZ_ROUTES:
+            # dz = dA * act'(z) and its partial sums were produced by the consumer's input-gradient launch
+            assert not bk.srcs[node.out], f"{node.name}: fused dz and separate gradient sources"
+            wdz, dz = form is GnBwd.DZ_WGRAD, bk.dz[node.out]
+            if gn:
+                # _n: per-channel sums, whose dgamma / dbeta join the batched launch at the end of backward
+                n, dst = ("_n", (L.ptr(e.dz_pc),)) if e.route.dz_n else ("", (dgamma, dbeta))
+                dzs, tab = ("_dz", (L.ptr(e.coef), L.ptr(e.dz_coef))) if wdz else ("", ())
+                L.call("mc_gn_act_bwd_finalize" + n + dzs, L.ptr(e.dz_part), N, e.route.dz_blocks, node.c_out, node.groups,
+                       o.H * o.W, L.ptr(gamma), L.ptr(e.m12), *dst, *tab, st)
+                if e.route.dz_n:
+                    bk.gp_jobs.append((L.ptr(e.dz_pc), N, node.c_out, dgamma, dbeta))
+            if wdz:              # dY is formed by the filter-gradient launch
+                x0, x1, _ = self._sources([self.T[i] for i in node.srcs])
+                L.call("mc_conv2d_wgrad_dz", C.byref(e.desc), x0, x1, C.byref(dz), L.ptr(e.Y), L.ptr(e.dz_coef),
+                       L.ptr(dY), L.ptr(e.wpart), st)
+            else:
+                L.call("mc_gn_bwd_apply_dz", C.byref(dz), L.ptr(e.Y), N, node.c_out, o.H, o.W, max(node.groups, 1),
+                       L.ptr(e.coef) if gn else None, L.ptr(e.m12), self.mc_dtype, L.ptr(dY), st)
+            return
+        gs = list(bk.srcs[node.out])
+        if node.pool > 1:
+            p = self.T[node.pooled]
+            for q in bk.srcs[node.pooled]:
+                assert q.kind in (L.GSRC_PADFOLD, L.GSRC_PLAIN) and q.c8_total == 0, "a pooled tensor feeds exactly one conv"
+                kind = L.GSRC_PADFOLD_POOL if q.kind == L.GSRC_PADFOLD else L.GSRC_PLAIN_POOL   # (PLAIN: learned-padding conv)
+                gs.append(L.GradSrc(q.ptr, kind, q.pad, q.pad_mode, node.pool, p.H, p.W))
+        assert 1 <= len(gs) <= 2, f"{node.name}: {len(gs)} gradient sources"
+        g0, g1 = C.byref(gs[0]), (C.byref(gs[1]) if len(gs) > 1 else None)
+        sfx, dra = self._drop(node)
+        if form is GnBwd.SMALL:
+            L.call("mc_gn_act_bwd_small" + sfx, L.ptr(e.Y), N, node.c_out, o.H, o.W, node.groups, L.ptr(e.stats),
+                   L.ptr(gamma), L.ptr(beta), act, self.mc_dtype, g0, g1, L.ptr(dY), L.ptr(e.pc), *dra, st)
+            bk.gp_jobs.append((L.ptr(e.pc), N, node.c_out, dgamma, dbeta))
+            return
+        if gn:
+            L.call("mc_gn_act_bwd_reduce" + sfx, L.ptr(e.Y), N, node.c_out, o.H, o.W, node.groups, L.ptr(e.stats), L.ptr(gamma),
+                   L.ptr(beta), node.post, act, self.mc_dtype, g0, g1, L.ptr(e.gpart), *dra, st)
+            L.call("mc_gn_act_bwd_finalize", L.ptr(e.gpart), N, e.gpart.shape[1], node.c_out, node.groups, o.H * o.W, L.ptr(gamma),
+                   L.ptr(e.m12), dgamma, dbeta, st)
+        L.call("mc_gn_act_bwd_apply" + sfx, L.ptr(e.Y), N, node.c_out, o.H, o.W, node.groups, L.ptr(e.stats), L.ptr(e.m12),
+               L.ptr(gamma), L.ptr(beta), node.post, act, self.mc_dtype, g0, g1, L.ptr(dY), *dra, st)
+
+    def _bwd_conv(self, e, bk):
+        """dY, the filter-gradient partials (combined at the end of backward) and the input gradients on the padded domain."""
+        self._bwd_gn(e, bk)
+        node, N, dY, dxp, st = e.node, self.N, self.dY, e.dxp, bk.st
+        srcs = [self.T[i] for i in node.srcs]
+        if e.route.gn_bwd is not GnBwd.DZ_WGRAD:
+            x0, x1, pro = self._sources(srcs)
+            L.call("mc_conv2d_wgrad_fused", C.byref(e.desc), x0, x1, pro, L.ptr(dY), L.ptr(e.wpart), st)
+        if not e.need_dgrad:
+            return
+        if e.route.epi >= 0:
+            # the source's GroupNorm-backward reduction rides in this launch: dz and its partial sums instead of dA
+            pe, s0, act = self.plan[e.route.epi], srcs[0], L.ACTS[self.g.act]
+            coef, blocks = (L.ptr(pe.coef) if pe.node.post == L.POST_GN_ACT else None), pe.route.dz_blocks
+            epi = L.ConvEpilogue(L.ptr(pe.Y), coef, act, node.pad, self.mode, s0.H, s0.W, L.ptr(pe.dz_part), blocks,
+                                 int(self.mc_dtype == L.MC_MIX16))
+            self._probe_begin()
+            L.call("mc_conv2d_fused", C.byref(e.ddesc), L.ptr(dY), None, None, L.ptr(e.dbank), None,
+                   L.ptr(dxp[0]), None, None, C.byref(epi), st)
+            self._probe_end(e.ddesc, "dgrad+dz " + node.name, extra_in=s0.C * s0.H * s0.W)
+            L.call("mc_fold_padded_dz", L.ptr(dxp[0]), N, s0.C, s0.H, s0.W, node.pad, self.mode, self.mc_dtype,
+                   L.ptr(pe.Y), coef, act, L.ptr(pe.dz_part), blocks, pe.route.dz_tiles, st)
+            bk.dz[node.srcs[0]] = L.GradSrc(L.ptr(dxp[0]), L.GSRC_PADFOLD, node.pad, self.mode, 1, s0.H, s0.W)
+            return
+        self._probe_begin()
+        L.call("mc_conv2d", C.byref(e.ddesc), L.ptr(dY), None, L.ptr(e.dbank), None, L.ptr(dxp[0]),
+               L.ptr(dxp[1]) if len(dxp) > 1 else None, None, st)
+        self._probe_end(e.ddesc, "dgrad " + node.name)
+        # adjoint of the padding: fold the halo onto the interior once, consumers read at an offset (the two outputs of
+        # a convolution over concatenated sources in one launch)
+        live = [(i, s, buf) for i, s, buf in zip(node.srcs, srcs, dxp) if s.requires_grad]
+        if len(live) == 2 and (live[0][1].H, live[0][1].W) == (live[1][1].H, live[1][1].W):
+            (_, a, abuf), (_, b, bbuf) = live
+            L.call("mc_fold_padded2", L.ptr(abuf), a.C, L.ptr(bbuf), b.C, N, a.H, a.W, node.pad, self.mode, self.mc_gdtype, st)
+        else:
+            for _, s, buf in live:
+                L.call("mc_fold_padded", L.ptr(buf), N, s.C, s.H, s.W, node.pad, self.mode, self.mc_gdtype, st)
+        for i, s, buf in live:
+            bk.srcs[i].append(L.GradSrc(L.ptr(buf), L.GSRC_PADFOLD, node.pad, self.mode, 1, s.H, s.W))
 
     def _pack_all_banks(self, params, st):
         """Forward and input-gradient banks of every layer in one batched launch per 24 jobs (weights are fixed
         within a step); the eight border banks of every learned-padding layer in one launch per 16 layers."""
-        jobs = []
-        for e in self.convs:
-            w = self._param(params, e["node"].name + "weight")
-            jobs.append((e["desc"], L.ptr(w), 0, L.ptr(e["bank"])))
-            if e["need_dgrad"]:
-                jobs.append((e["desc"], L.ptr(w), 1, L.ptr(e["dbank"])))
-        for e in self.learned:                               # main banks: forward as launched (fdesc), gradient of the valid conv
-            w = self._param(params, e["node"].name + "conv.weight")
-            jobs.append((e["fdesc"], L.ptr(w), 0, L.ptr(e["bank"])))
-            if e["need_dgrad"]:
-                jobs.append((e["desc"], L.ptr(w), 1, L.ptr(e["dbank"])))
-        n = len(jobs)
-        if n:
-            descs = (L.ConvDesc * n)(*[j[0] for j in jobs])
-            ws = (C.c_void_p * n)(*[j[1] for j in jobs])
-            dg = (C.c_int32 * n)(*[j[2] for j in jobs])
-            outs = (C.c_void_p * n)(*[j[3] for j in jobs])
-            L.call("mc_pack_weights_batched", descs, ws, dg, outs, n, st)
+        jobs = []        # (a learned layer's main bank: forward as launched (fdesc), gradient of the valid conv)
+        for e, fdesc, wname in ([(e, e.desc, "weight") for e in self.convs] + [(e, e.fdesc, "conv.weight") for e in self.learned]):
+            w = L.ptr(self._param(params, e.node.name + wname))
+            jobs.append((fdesc, w, 0, L.ptr(e.bank)))
+            if e.need_dgrad:
+                jobs.append((e.desc, w, 1, L.ptr(e.dbank)))
+        if jobs:
+            L.call("mc_pack_weights_batched", *_columns(jobs, L.ConvDesc, C.c_void_p, C.c_int32, C.c_void_p), len(jobs), st)
         n = len(self.learned)
         if n:
-            descs = (L.LearnedDesc * n)(*[e["ldesc"] for e in self.learned])
-            ws = (C.c_void_p * (8 * n))(*[L.ptr(self._param(params, e["node"].name + b + ".weight"))
+            descs, fw, dg = _columns([(e.ldesc, L.ptr(e.lbank), L.ptr(e.ldbank)) for e in self.learned],
+                                     L.LearnedDesc, C.c_void_p, C.c_void_p)
+            ws = (C.c_void_p * (8 * n))(*[L.ptr(self._param(params, e.node.name + b + ".weight"))
                                           for e in self.learned for b in L.LEARNED_FRAME_BANKS])
-            fw = (C.c_void_p * n)(*[L.ptr(e["lbank"]) for e in self.learned])
-            dg = (C.c_void_p * n)(*[L.ptr(e["ldbank"]) for e in self.learned])
             L.call("mc_learned_pack_banks_batched", descs, ws, fw, dg, n, st)
 
     # -------------------------------------------------------------- measurement hooks (bench.py)
-    _probe = None
-
     def enable_probe(self, passes: int = 3):
         """Record a HIP-event pair (on the launch stream) around every mc_conv2d launch.  The timing events are created and
         recorded once up front: creating them lazily stalled the host for ~80 ms when the runtime grew its signal pool in the
         middle of a pass, and that stall landed inside one event pair (round 2: a 7 ms "launch" of a 50 us kernel)."""
         self._probe = []
-        n = 2 * (2 * len(getattr(self, "convs", [])) + 8) * max(passes, 1)
+        n = 2 * (2 * len(self.convs) + 8) * max(passes, 1)
         self._probe_pool = [torch.cuda.Event(enable_timing=True) for _ in range(n)]
         for ev in self._probe_pool:
             ev.record()
@@ -1319,7 +1457,7 @@ class Engine:
         self._probe_pool = []
 
     def _probe_event(self):
-        ev = self._probe_pool.pop() if getattr(self, "_probe_pool", None) else torch.cuda.Event(enable_timing=True)
+        ev = self._probe_pool.pop() if self._probe_pool else torch.cuda.Event(enable_timing=True)
         ev.record()
         return ev
 
@@ -1384,14 +1522,10 @@ class Engine:
         """3 s (sum_in + sum_out over the conv layers) + s_io (C_i + 2 C_o) H W."""
         s = 2 if (precision or self.precision) in ("bf16", "mixed") else 4
         tot = 0
-        for e in self.plan:
-            if e["node"].kind != "conv":
-                continue
-            if e["node"].learned or e["node"].spectral:      # (a spectral layer reads its input once and writes its output once)
-                src, o = self.T[e["node"].srcs[0]], self.T[e["node"].out]
-                tot += src.C * src.H * src.W + o.C * o.H * o.W
-                continue
-            d = e["desc"]
+        for e in self.learned + self.spectral:      # (a spectral layer reads its input once and writes its output once)
+            src, o = self.T[e.node.srcs[0]], self.T[e.node.out]
+            tot += src.C * src.H * src.W + o.C * o.H * o.W
+        for d in (e.desc for e in self.convs):
             ho, wo = d.h + 2 * d.pad - d.k + 1, d.w + 2 * d.pad - d.k + 1
             tot += (d.c_in0 + d.c_in1) * d.h * d.w + d.c_out * ho * wo
         # (s_io = s: SURVEY §8d prices the boundary tensors in the storage type as well; round 2 used 4 bytes here, which
@@ -1401,11 +1535,9 @@ class Engine:
     def activation_bytes(self) -> int:
         tot = 0
         for e in self.plan:
-            for k in ("Y", "dsrc"):
-                if k in e:
-                    tot += e[k].numel() * e[k].element_size()
-            for b in e.get("dxp", []):
-                tot += b.numel() * b.element_size()
+            for b in (getattr(e, "Y", None), getattr(e, "dsrc", None), *getattr(e, "dxp", ())):
+                if b is not None:
+                    tot += b.numel() * b.element_size()
         for t in self.T.values():
             if t.buf is not None:
                 tot += t.buf.numel() * t.buf.element_size()

@@ -3,7 +3,7 @@
 width k + 1 / k) framed together, plus one shared bias.
 
 Stand-alone, the layer is a one-node graph on the engine (engine.single_layer_graph(learned=True, input_grad=True)), as
-SymmetricConv2d and FluidLayer are: Engine._plan_learned / _learned_forward / _learned_backward are the only executor of
+SymmetricConv2d and FluidLayer are: Engine._plan_learned / _fwd_learned / _bwd_learned are the only executor of
 the layer, inside a network or alone.  The main bank runs on the library's conv kernels (`mc_conv2d`, `mc_conv2d_wgrad*`)
 as a zero-padded 'same' convolution straight into the output (its interior is the valid result); the frame of the eight
 border banks -- forward, filter gradient and input gradient -- is one `mc_learned_frame_*` launch per direction that reads

@@ -91,7 +91,7 @@ def test_plan_gathers_the_gradient_of_unaligned_operands(r_p):
         e = E.Engine(g, prec)
         e.configure(2, 128, 506, torch.device("cpu"))
         for p in e.plan:
-            node = p["node"]
+            node = p.node
             if node.kind == "cat":
                 off, want = 0, {}
                 for k, t in enumerate(node.srcs):
@@ -99,15 +99,17 @@ def test_plan_gathers_the_gradient_of_unaligned_operands(r_p):
                     if off % 8 or (k < len(node.srcs) - 1 and c % 8):
                         want[t] = off
                     off += c
-                assert {t: v[0] for t, v in p["gather"].items()} == want
-                for t, (_, buf) in p["gather"].items():
+                assert {t: v[0] for t, v in p.gather.items()} == want
+                for t, (_, buf) in p.gather.items():
                     T = e.T[t]
                     assert tuple(buf.shape) == (2, (T.C + 7) // 8, T.H, T.W, 8) and buf.dtype == e.g_dtype
             elif node.kind == "conv" and node.post == 2 and node.gn_name:
                 if node.c_out // node.groups not in (1, 2, 4, 8):
-                    assert "pc" not in p and "dz_pc" not in p, node.name
+                    r = p.route
+                    assert r.gn_fwd is not E.GnFwd.SMALL and r.gn_bwd is not E.GnBwd.SMALL and not r.dz_n, node.name
+                    assert getattr(p, "pc", None) is None and getattr(p, "dz_pc", None) is None, node.name
         if r_p == "learned":
-            assert [len(p["gather"]) for p in e.plan if p["node"].kind == "cat"] == [0, 2, 2, 2]
+            assert [len(p.gather) for p in e.plan if p.node.kind == "cat"] == [0, 2, 2, 2]
 
 
 def test_fluid_trunk_accepts_any_width():

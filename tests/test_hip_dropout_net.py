@@ -203,12 +203,12 @@ def test_dropout_nodes_are_materialised_and_keep_their_own_backward(monkeypatch,
         g = _net(drop)._graph
         eng = Engine(g, prec)
         eng.configure(*NET_SHAPE[:1], *NET_SHAPE[2:], torch.device(DEV))
-        trunk = [e for e in eng.plan if e["node"].kind == "conv" and e["node"].name.startswith(("conv.0.", "convs."))]
+        trunk = [e for e in eng.plan if e.node.kind == "conv" and e.node.name.startswith(("conv.0.", "convs."))]
         assert len(trunk) == 5
-        found[drop] = [(eng.T[e["node"].out].fused, "dz_blocks" in e, any(o.get("epi") is e for o in eng.plan)) for e in trunk]
+        found[drop] = [(eng.T[e.node.out].fused, e.route.dz_blocks > 0, any(o.route.epi >= 0 and eng.plan[o.route.epi] is e for o in eng.convs)) for e in trunk]
         if drop:
-            assert all(e["node"].drop == P for e in trunk)
-            assert eng.drop_state is not None and eng.T[trunk[0]["node"].out].buf is not None
+            assert all(e.node.drop == P for e in trunk)
+            assert eng.drop_state is not None and eng.T[trunk[0].node.out].buf is not None
         else:
             assert eng.drop_state is None
     assert not any(any(t) for t in found[P]), found[P]

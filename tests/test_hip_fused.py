@@ -76,7 +76,7 @@ def test_fused_network_matches_unfused(monkeypatch, kind, r_p, precision):
     y3, g3, m3 = _run(monkeypatch, 3, kind, r_p, precision)
     fused = [t for t in m3.engine().T.values() if t.fused]
     assert fused and not any(t.fused for t in m0.engine().T.values())
-    assert any("epi" in e for e in m3.engine().plan), "no input-gradient launch carries the GroupNorm-backward epilogue"
+    assert any(e.route.epi >= 0 for e in m3.engine().convs), "no input-gradient launch carries the GroupNorm-backward epilogue"
     def check(gk, what):
         if precision == "fp32":
             worst = max((rel_l2(gk[n], g0[n]), n) for n in g0)
@@ -106,7 +106,7 @@ def test_fused_network_matches_unfused(monkeypatch, kind, r_p, precision):
         monkeypatch.setenv("MANTLE_FUSE_DZ_RR", "1")
         yk, gk, mk = _run(monkeypatch, 0, kind, r_p, precision)
         assert torch.equal(y0, yk)
-        assert any("epi" in e for e in mk.engine().plan) == (kind == "unet16w")
+        assert any(e.route.epi >= 0 for e in mk.engine().convs) == (kind == "unet16w")
         check(gk, "dz_rr")
 
 

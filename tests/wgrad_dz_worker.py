@@ -39,7 +39,7 @@ def main(out):
         tr = trainer(False)
         tr.train_step(gVTp, uvp, yc, paras, scaler)
         torch.cuda.synchronize()
-        res[name + "_layers"] = np.int64(sum("dz_coef" in e for e in tr.model_uvp.engine().plan))
+        res[name + "_layers"] = np.int64(sum(e.dz_coef is not None for e in tr.model_uvp.engine().convs))
         res[name + "_eager_grad"] = tr.flat.grad.cpu().numpy()
         res[name + "_eager_param"] = tr.flat.param.cpu().numpy()
         tg = trainer(True)
