@@ -652,6 +652,29 @@ int mc_ensemble_snapshot(const float* T_new, const double* t, const int32_t* fla
                          int32_t* count, int32_t* missed, int32_t* slot, int32_t capacity, int32_t b, int32_t h, int32_t w,
                          float* snaps, double* snap_t, void* stream);
 
+/* ---- rollout scoring: ensemble members against the snapshots of their simulations ("Rollout scoring") ----
+ * One launch BETWEEN mc_rollout_step and mc_rollout_finalize: T_prev, T_next [b][h][w] are the state before / after the step,
+ * t is still the old clock; dt, flags of mc_rollout_dt.  truth [b][capacity][h][w] f32 and truth_t [b][capacity] f64 hold the
+ * later snapshots of member m's simulation and their simulated times, ascending; only the first min(n_truth[m], capacity)
+ * count.  Returns MC_EINVAL, launching nothing, for a null pointer, b <= 0 or b > 65535, h < 5 or w < 5, capacity <= 0 or
+ * T_prev == T_next.  The library allocates nothing.
+ * Member m with flags[m] = 0 is not touched.  Otherwise t0 = t[m], t1 = flags[m] == 2 ? t_end[m] : t0 + dt[m] (bitwise the
+ * clock mc_rollout_finalize stores), and from k = next[m] on, while k < min(n_truth[m], capacity) and tau = truth_t[m][k] <= t1:
+ * tau < t0 (a time the clock had passed already) counts in skipped[m] and leaves row k as it is; else row k is scored with
+ * theta = t1 > t0 ? (tau - t0) / (t1 - t0) : 0 and counts in scored[m]; k += 1.  Then next[m] = k.  Any number of times may
+ * fall into one step.
+ * Scoring row k, over ALL h x w cells, every operation in f64: a = (double)T_prev + theta * ((double)T_next - (double)T_prev),
+ * b = (double)truth[m][k].  Pass 1: row means A_i, B_i -- lane l adds columns l, l + 64, ... in ascending order, then the xor
+ * tree, then / w -- and Abar = (sum_i A_i) / h, Bbar likewise, i ascending.  Pass 2, the same order inside a row and rows added
+ * with i ascending: sum|a-b|, max|a-b|, Saa = sum (a-Abar)^2, Sbb = sum (b-Bbar)^2, Sab = sum (a-Abar)(b-Bbar).
+ * table [b][capacity][8] row = (tau, theta, mae = sum|a-b| / (h w), max_err, corr = Sab / sqrt(Saa Sbb) (NaN when
+ * Saa Sbb == 0), prof_mae = (sum_i |A_i - B_i|) / h, Abar, Bbar); prof [b][capacity][2][h] = (A_i, B_i).  One workgroup per
+ * member: a member's rows depend on its own data alone, whatever b is. */
+int mc_score_rollout(const float* T_prev, const float* T_next, const double* t, const double* dt, const int32_t* flags,
+                     const double* t_end, const float* truth, const double* truth_t, const int32_t* n_truth, int32_t capacity,
+                     int32_t b, int32_t h, int32_t w, int32_t* next, int32_t* scored, int32_t* skipped, double* table, double* prof,
+                     void* stream);
+
 /* ---- series scoring: a trained Stokes net against the snapshots of a simulation ("Series scoring") ----
  * Store (f32, device): T, u, v [n_snap][h][w] with snapshot stride store_stride (un-scaled, as the files hold them), sim [n_snap]
  * int32 (the snapshot's simulation), prev [n_snap] int32 (its baseline snapshot; outside [0, n_snap) = none), paras [n_sims][3] =

@@ -9,6 +9,13 @@ list with no host synchronisation inside the loop.
     python -m pbml_mantle_convection_amd.evaluate --weights sd.pt -l 5 -f 16 -r 6 -k 5 -p zeros --data_dir DIR --an cv \
         [--sims 3 7] [--every 1] [--batch 32] [--precision bf16] [--graph 1] --out DIR
     python -m pbml_mantle_convection_amd.evaluate --synthetic 64 128 506 --out DIR        # seeded fields instead of files
+
+Rollout scoring (DESIGN.md §9 "Rollout scoring"): with --rollout_steps N the coupled loop (net + advection-diffusion step) of
+the checkpoint starts from snapshot --start of every selected simulation and is scored against the later snapshots at their
+own simulated times (times.pt) by rollout.EnsembleRollout(score_capacity=...):
+
+    python -m pbml_mantle_convection_amd.evaluate --weights sd.pt ... --data_dir DIR --an cv --rollout_steps 5000 \
+        [--start 0] [--truth_every 10] [--truth_count 16] [--t_end X] --out DIR
 """
 import argparse
 import csv
@@ -20,7 +27,8 @@ import torch
 
 from . import _lib as L
 from .datasetio import _GridMixin, _load, _selected_sims
-from .rollout import build_stokes, normalise_params, synthetic_ensemble
+from .rollout import SCORE_NAMES as ROLLOUT_SCORE_NAMES
+from .rollout import EnsembleRollout, build_stokes, normalise_params, synthetic_ensemble
 from .scaler import velocity_scaler
 
 SCORE_NAMES = ("mae_u", "mae_v", "base_u", "base_v", "max_u", "max_v", "maxerr_u", "maxerr_v", "mass_pred", "mass_true")
@@ -154,6 +162,109 @@ def synthetic_series(N, H, W, seed=0):
         v[n] = -0.5 * (psi[1:-1, 2:] - psi[1:-1, :-2]) * scale[s]
     return dict(T=T[:, 0], u=u.astype(np.float32), v=v.astype(np.float32), sim=sim, prev=previous_snapshots(sim), raq=raq, fkt=fkt,
                 fkp=fkp, xc=xc, yc=yc)
+
+
+def load_rollout_truth(data_dir, an, sims=None, start=0, every=1, count=None):
+    """One ensemble member per selected simulation of split `an` in the reference's layout: T0 = snapshot `start` of
+    `e1_Tprev_data.pt`, truth = snapshots start + every, start + 2 every, ... (at most `count` of them) with the simulated times
+    t = times[k] - times[start] from `times.pt` (snapshot i carries times[i], as the datasets pair them).  The mesh is loaded the
+    way load_series loads it and mixed meshes are refused as there.  Series of different length are padded: n[m] holds the
+    length, the padding times are +inf and the padding fields 0.  Returns the arguments of EnsembleRollout.reset -- T0
+    [B,1,H,W], xc, yc, ycc, raq, fkt, fkp, nd, truth = dict(T [B,S,H,W], t [B,S], n [B]) -- plus sim_ids."""
+    start, every = int(start), int(every)
+    if start < 0 or every < 1 or (count is not None and int(count) < 1):
+        raise ValueError("start must be non-negative, every and count at least 1")
+    want = None if sims is None else {int(s) for s in sims}
+    T0, Tt, tt, raq, fkt, fkp, ids = [], [], [], [], [], [], []
+    xc = yc = None
+    for entry, d in _selected_sims(str(data_dir), an):
+        if want is not None and int(entry[0]) not in want:
+            continue
+        g = _Grid()
+        g._load_grid(d)
+        gx, gy = g.xc[0].numpy(), g.yc[0].numpy()
+        if xc is None:
+            xc, yc = gx, gy
+        elif gx.shape != xc.shape or not (np.array_equal(gx, xc) and np.array_equal(gy, yc)):
+            raise ValueError(f"an ensemble lives on one mesh: simulation {entry[0]} lies on another mesh than simulation {ids[0]}")
+        H, W = xc.shape
+        Ts = _load(d + "/e1_Tprev_data.pt").reshape(-1, H, W).float().numpy()
+        times = torch.as_tensor(_load(d + "/times.pt")).to(torch.float64).reshape(-1).numpy()[:Ts.shape[0]]
+        n_snap = min(Ts.shape[0], times.shape[0])
+        if start >= n_snap:
+            raise ValueError(f"{d}: snapshot {start} asked for, the series holds {n_snap}")
+        ks = np.arange(start + every, n_snap, every)[:None if count is None else int(count)]
+        T0.append(Ts[start]); Tt.append(Ts[ks]); tt.append(times[ks] - times[start])
+        raq.append(float(entry[2])); fkt.append(float(entry[3])); fkp.append(float(entry[4]))
+        ids.append(int(entry[0]))
+    if not ids:
+        raise ValueError(f"no simulation of split {an!r}" + (f" among {sorted(want)}" if want is not None else "") + f" under {data_dir}")
+    B, S = len(ids), max(a.shape[0] for a in Tt)
+    if S == 0:
+        raise ValueError(f"no snapshot after snapshot {start} with every = {every}")
+    T = np.zeros((B, S, H, W), dtype=np.float32)
+    t = np.full((B, S), np.inf, dtype=np.float64)
+    n = np.zeros(B, dtype=np.int32)
+    for m in range(B):
+        n[m] = Tt[m].shape[0]
+        T[m, :n[m]], t[m, :n[m]] = Tt[m], tt[m]
+    raq, fkt, fkp = np.asarray(raq), np.asarray(fkt), np.asarray(fkp)
+    return dict(T0=np.stack(T0)[:, None].astype(np.float32), xc=xc, yc=yc, ycc=yc, raq=raq, fkt=fkt, fkp=fkp,
+                nd=normalise_params(np.stack([raq, fkt, fkp], 1)), truth=dict(T=T, t=t, n=n), sim_ids=ids)
+
+
+def synthetic_rollout_truth(B, S, H, W, seed=0):
+    """Seeded stand-in for load_rollout_truth: initial and "simulated" fields from rollout.synthetic_ensemble, parameters that
+    differ from member to member, and ascending times in pairs 1 % of a diffusive step apart (so two of them fall into one CFL
+    step), the pairs three diffusive steps apart and shifted from member to member."""
+    T0, xc, yc = synthetic_ensemble(B, H, W, seed=seed)
+    T = synthetic_ensemble(B * S, H, W, seed=seed + 1)[0].reshape(B, S, H, W)
+    dx, dy = 4.0 / (W - 2), 1.0 / (H - 2)
+    step = 0.5 * dx * dx * dy * dy / (dx * dx + dy * dy)           # the diffusive limit of the explicit step: no CFL step is longer
+    k = np.arange(S)
+    t = (3.0 * step * (k // 2 + 1) + 0.01 * step * (k % 2))[None, :] * (1.0 + 0.125 * np.arange(B))[:, None]
+    raq = np.array([1.5, 2.5, 4.0, 3.0])[np.arange(B) % 4]
+    fkt = np.array([1e6, 1e7, 1e8, 1e7])[np.arange(B) % 4]
+    fkp = np.array([10.0, 30.0, 60.0, 20.0])[np.arange(B) % 4]
+    return dict(T0=T0, xc=xc, yc=yc, ycc=yc, raq=raq, fkt=fkt, fkp=fkp, nd=normalise_params(np.stack([raq, fkt, fkp], 1)),
+                truth=dict(T=T, t=t.astype(np.float64), n=np.full(B, S, dtype=np.int32)), sim_ids=list(range(B)))
+
+
+def summarise_rollout(score, level=0.9, sim_ids=None):
+    """One dict per member from run()["score"] (tensors or arrays): the number of scored rows, the mean of mae over them, corr
+    and prof_mae of the last scored row, the mean of |T_mean_pred - T_mean_true| (the three figures the reference's evaluation
+    notebook puts into its titles) and the horizon: the first truth time whose corr is below `level`, inf if none is."""
+    table = score["table"]
+    table = np.asarray(table.cpu() if isinstance(table, torch.Tensor) else table, dtype=np.float64)
+    col = {name: q for q, name in enumerate(ROLLOUT_SCORE_NAMES)}
+    out = []
+    for m in range(table.shape[0]):
+        rows = table[m][~np.isnan(table[m][:, col["t"]])]
+        d = dict(member=m if sim_ids is None else int(sim_ids[m]), scored=int(rows.shape[0]), level=float(level))
+        if rows.shape[0]:
+            low = rows[rows[:, col["corr"]] < level]
+            d.update(mae=float(rows[:, col["mae"]].mean()), corr_last=float(rows[-1, col["corr"]]),
+                     prof_mae_last=float(rows[-1, col["prof_mae"]]),
+                     T_mean_mae=float(np.abs(rows[:, col["T_mean_pred"]] - rows[:, col["T_mean_true"]]).mean()),
+                     t_last=float(rows[-1, col["t"]]), horizon=float(low[0, col["t"]]) if low.shape[0] else float("inf"))
+        else:
+            nan = float("nan")
+            d.update(mae=nan, corr_last=nan, prof_mae_last=nan, T_mean_mae=nan, t_last=nan, horizon=float("inf"))
+        out.append(d)
+    return out
+
+
+def write_rollout_scores(out_dir, score, summary, sim_ids=None):
+    """rollout_scores.npz (table, names, prof, scored, skipped, next, sim) and rollout_summary.json (one line) under out_dir."""
+    os.makedirs(out_dir, exist_ok=True)
+    arr = lambda v: np.asarray(v.cpu() if isinstance(v, torch.Tensor) else v)  # noqa: E731
+    npz, js = os.path.join(out_dir, "rollout_scores.npz"), os.path.join(out_dir, "rollout_summary.json")
+    B = arr(score["table"]).shape[0]
+    np.savez(npz, names=np.asarray(ROLLOUT_SCORE_NAMES), sim=np.asarray(list(range(B)) if sim_ids is None else sim_ids),
+             **{k: arr(score[k]) for k in ("table", "prof", "scored", "skipped", "next")})
+    with open(js, "w") as fh:
+        fh.write(json.dumps(summary) + "\n")
+    return npz, js
 
 
 class SeriesScorer:
@@ -294,6 +405,13 @@ def build_arg_parser():
                    help="seeded synthetic grid, fields and velocities instead of --data_dir")
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--device", type=str, default="cuda:0")
+    p.add_argument("--rollout_steps", type=int, default=0,
+                   help="N > 0: score the coupled rollout of N steps against the simulations instead -> rollout_scores.npz")
+    p.add_argument("--start", type=int, default=0, help="rollout scoring: the snapshot the members start from")
+    p.add_argument("--truth_every", type=int, default=1, help="rollout scoring: score against every k-th later snapshot")
+    p.add_argument("--truth_count", type=int, default=None, help="rollout scoring: at most this many snapshots per member")
+    p.add_argument("--t_end", type=float, default=None, help="rollout scoring: simulated time at which every member stops")
+    p.add_argument("--level", type=float, default=0.9, help="rollout scoring: the horizon is the first time with corr below it")
     return p
 
 
@@ -334,6 +452,8 @@ def summarise(table, sim, sim_ids=None):
 
 def main(argv=None):
     a = build_arg_parser().parse_args(argv)
+    if a.rollout_steps:
+        return rollout_main(a)
     if a.synthetic:
         arrays = synthetic_series(*a.synthetic, seed=a.seed)
     elif a.data_dir:
@@ -351,6 +471,30 @@ def main(argv=None):
     for ln in lines:
         print(json.dumps(ln), flush=True)
     return lines
+
+
+def rollout_main(a):
+    """--rollout_steps N: truth from the files (or seeded), the ensemble rollout of the checkpoint, scores and summary."""
+    if a.rollout_steps < 0:
+        raise SystemExit("--rollout_steps must be positive")
+    if a.synthetic:
+        args = synthetic_rollout_truth(a.synthetic[0], a.truth_count or 4, a.synthetic[1], a.synthetic[2], seed=a.seed)
+    elif a.data_dir:
+        args = load_rollout_truth(a.data_dir, a.an, sims=a.sims, start=a.start, every=a.truth_every, count=a.truth_count)
+    else:
+        raise SystemExit("give --data_dir DIR or --synthetic B H W")
+    ids = args.pop("sim_ids")
+    dev = torch.device(a.device)
+    L.load()
+    ro = EnsembleRollout(build_stokes(a, dev), dev, precision=a.precision, use_graph=bool(a.graph),
+                         score_capacity=int(args["truth"]["T"].shape[1]))
+    ro.reset(**{k: (v if isinstance(v, dict) else torch.as_tensor(v)) for k, v in args.items()}, t_end=a.t_end)
+    out = ro.run(a.rollout_steps)
+    summary = dict(steps=a.rollout_steps, t=out["t"].cpu().tolist(), scored=out["score"]["scored"].cpu().tolist(),
+                   skipped=out["score"]["skipped"].cpu().tolist(), members=summarise_rollout(out["score"], a.level, ids))
+    write_rollout_scores(a.out, out["score"], summary, ids)
+    print(json.dumps(summary), flush=True)
+    return summary
 
 
 if __name__ == "__main__":

@@ -8,7 +8,7 @@ synchronisation inside the loop; six diagnostics per member and step are accumul
 
     python -m pbml_mantle_convection_amd.rollout --params params.csv --steps 100 --out DIR --synthetic 8 128 506 \
         -l 5 -f 16 -r 6 -k 5 -p zeros [--weights sd.pt] [--t_end X] [--snapshot_every K] [--precision bf16] \
-        [--profiles 1 [--t_avg_start X]] [--save_every DT --save_capacity S]
+        [--profiles 1 [--t_avg_start X]] [--save_every DT --save_capacity S] [--truth truth.npz [--score_capacity S]]
 """
 import argparse
 import json
@@ -22,6 +22,7 @@ from .datasetio import normalise_parameters
 
 HIST_NAMES = ("t", "dt", "T_mean", "v_rms", "Nu_bot", "Nu_top", "T_min", "T_max")
 PROFILE_NAMES = ("T", "u2", "v2", "vT")           # rows of a depth profile: means over a row of T, (s u)^2, (s v)^2, (s v) T
+SCORE_NAMES = ("t", "theta", "mae", "max_err", "corr", "prof_mae", "T_mean_pred", "T_mean_true")   # columns of a score row
 HIST_CHUNK = 256          # rows of the device-side history buffer the captured step writes into
 
 
@@ -52,6 +53,31 @@ def broadcast_member_value(value, B, name, default=0.0):
     if t.numel() != B:
         raise ValueError(f"{name} must be None, a number or hold one value per member ({B}), got {t.numel()} values")
     return t.clone()
+
+
+def check_truth(truth, B, H, W, capacity):
+    """truth = dict(T=[B,S,H,W], t=[B,S], n=[B] or None) with S <= capacity -> (T f32 [B,S,H,W], t f64 [B,S], n int32 [B]) on
+    the host.  Within its first n[m] entries a member's times are finite, non-negative and strictly ascending."""
+    if not isinstance(truth, dict) or "T" not in truth or "t" not in truth:
+        raise ValueError("truth must be a dict with T [B,S,H,W], t [B,S] and optionally n [B]")
+    T = torch.as_tensor(truth["T"]).detach().cpu()
+    t = torch.as_tensor(truth["t"]).detach().cpu().to(torch.float64)
+    if T.dim() != 4 or tuple(T.shape[:1] + T.shape[2:]) != (B, H, W):
+        raise ValueError(f"truth['T'] must be [{B},S,{H},{W}], got {tuple(T.shape)}")
+    S = int(T.shape[1])
+    if S < 1 or S > capacity:
+        raise ValueError(f"truth holds {S} snapshots per member, score_capacity is {capacity}")
+    if tuple(t.shape) != (B, S):
+        raise ValueError(f"truth['t'] must be [{B},{S}], got {tuple(t.shape)}")
+    n = truth.get("n")
+    n = torch.full((B,), S, dtype=torch.int64) if n is None else torch.as_tensor(n).detach().cpu().reshape(-1).to(torch.int64)
+    if n.numel() != B or bool((n < 0).any()) or bool((n > S).any()):
+        raise ValueError(f"truth['n'] must hold one count in [0, {S}] per member ({B})")
+    for m in range(B):
+        tm = t[m, :int(n[m])]
+        if not bool(torch.isfinite(tm).all()) or bool((tm < 0).any()) or bool((tm[1:] <= tm[:-1]).any()):
+            raise ValueError(f"truth['t'][{m}] must be finite, non-negative and strictly ascending within its {int(n[m])} entries")
+    return T.to(torch.float32), t, n.to(torch.int32)
 
 
 def parse_params_csv(path):
@@ -120,18 +146,27 @@ class EnsembleRollout:
     `profiles=True` adds mc_ensemble_profiles to the step: the horizontally averaged T, (s u)^2, (s v)^2 and (s v) T of the
     state every step starts from, and their time-weighted sums from t_avg_start[b] on.  `save_capacity=S > 0` adds
     mc_ensemble_snapshot: up to S fields per member and run, saved when the member's own clock passes its next saving time
-    (save_every[b] apart).  With both off the step issues the same launches as before and nothing else changes."""
+    (save_every[b] apart).  With both off the step issues the same launches as before and nothing else changes.
 
-    def __init__(self, stokes, device, CN_max=0.1, precision=None, use_graph=True, profiles=False, save_capacity=0):
+    `score_capacity=S > 0` adds mc_score_rollout between the step and its finalize: each member carries up to S later
+    snapshots of its simulation with their simulated times (reset(..., truth=...)), and the step in which the member's own
+    clock passes one of those times scores the member's temperature, interpolated linearly in time between the state before
+    and after the step, against that snapshot (SCORE_NAMES).  With score_capacity = 0 nothing is allocated or launched."""
+
+    def __init__(self, stokes, device, CN_max=0.1, precision=None, use_graph=True, profiles=False, save_capacity=0,
+                 score_capacity=0):
         self.stokes, self.CN_max, self.use_graph = stokes, float(CN_max), bool(use_graph)
         self.device = device if isinstance(device, torch.device) else torch.device(device)
         if isinstance(save_capacity, bool) or int(save_capacity) != save_capacity or int(save_capacity) < 0:
             raise ValueError(f"save_capacity must be a non-negative integer, got {save_capacity!r}")
-        self.profiles, self.save_capacity = bool(profiles), int(save_capacity)
+        if isinstance(score_capacity, bool) or int(score_capacity) != score_capacity or int(score_capacity) < 0:
+            raise ValueError(f"score_capacity must be a non-negative integer, got {score_capacity!r}")
+        self.profiles, self.save_capacity, self.score_capacity = bool(profiles), int(save_capacity), int(score_capacity)
         if precision is not None:
             stokes.set_precision(precision)
         self._s = None          # member state
         self._x = None          # statistics of the members (profiles / save_capacity): the captured step reads them by address
+        self._sc = None         # truth and scores of the members (score_capacity): read and written by address as well
         self._g = None          # grid, parameters, work buffers and the captured step of one (B, H, W)
 
     # ---- member state ---------------------------------------------------------------------------------------------
@@ -152,18 +187,30 @@ class EnsembleRollout:
                 if S:
                     self._x.update(snaps=torch.zeros((B, S, H, W), dtype=torch.float32, device=dev),
                                    snap_t=torch.full((B, S), float("nan"), **f64))
+            if self.score_capacity:
+                f64, i32, S = dict(dtype=torch.float64, device=dev), dict(dtype=torch.int32, device=dev), self.score_capacity
+                self._sc = dict(truth=torch.zeros((B, S, H, W), dtype=torch.float32, device=dev),
+                                truth_t=torch.full((B, S), float("inf"), **f64), n=torch.zeros(B, **i32), next=torch.zeros(B, **i32),
+                                scored=torch.zeros(B, **i32), skipped=torch.zeros(B, **i32),
+                                table=torch.full((B, S, len(SCORE_NAMES)), float("nan"), **f64),
+                                prof=torch.full((B, S, 2, H), float("nan"), **f64))
         return self._s
 
     STATS_KEYS = ("acc", "weight", "count", "next_save")
+    SCORE_KEYS = ("next", "scored", "skipped", "table", "prof")
 
     def state(self):
         """Copies of T, t, t_end, steps: enough to stop a study and continue it (load_state) on the same grid and parameters.
-        With profiles or timed saves on, also "stats": the time sums acc [B,4,H], their weight [B] and count [B], next_save [B]."""
+        With profiles or timed saves on, also "stats": the time sums acc [B,4,H], their weight [B] and count [B], next_save [B];
+        with scoring on, also "score": next, scored, skipped [B], table [B,S,8], prof [B,S,2,H] (the truth itself comes from
+        reset)."""
         if self._s is None:
             raise RuntimeError("no state: call reset() or load_state() first")
         st = {k: v.clone() for k, v in self._s.items()}
         if self._x is not None:
             st["stats"] = {k: self._x[k].clone() for k in self.STATS_KEYS}
+        if self._sc is not None:
+            st["score"] = {k: self._sc[k].clone() for k in self.SCORE_KEYS}
         return st
 
     def load_state(self, state):
@@ -190,16 +237,29 @@ class EnsembleRollout:
                 if v.numel() != self._x[k].numel():
                     raise ValueError(f"state['stats'][{k!r}] must hold {tuple(self._x[k].shape)}")
                 self._x[k].copy_(v.reshape(self._x[k].shape).to(self._x[k].dtype))
+        score = state.get("score")
+        if score is not None:
+            if self._sc is None:
+                raise ValueError("state['score'] needs a rollout built with score_capacity > 0")
+            for k in self.SCORE_KEYS:
+                v = torch.as_tensor(score[k])
+                if v.numel() != self._sc[k].numel():
+                    raise ValueError(f"state['score'][{k!r}] must hold {tuple(self._sc[k].shape)}")
+            for k in self.SCORE_KEYS:
+                self._sc[k].copy_(torch.as_tensor(score[k]).reshape(self._sc[k].shape).to(self._sc[k].dtype))
         return self
 
     # ---- grid and parameters --------------------------------------------------------------------------------------
     @torch.no_grad()
-    def reset(self, T0, xc, yc, ycc, raq, fkt, fkp, nd, t_end=None, t_avg_start=None, save_every=None):
+    def reset(self, T0, xc, yc, ycc, raq, fkt, fkp, nd, t_end=None, t_avg_start=None, save_every=None, truth=None):
         """T0 [B,1,H,W]; xc, yc, ycc [H,W] (ycc: the depth coordinate of the viscosity law, TS's `ycc`); raq, fkt, fkp [B];
         nd [B,3] their normalised values (normalise_params); t_end None | number | [B].  Clocks and step counts restart at 0.
         t_avg_start None (= 0) | number | [B]: the time from which the profiles are averaged (needs profiles=True);
         save_every None (= never) | number | [B]: the simulated time between two timed saves (needs save_capacity > 0).  The
-        time sums and the save counters restart at 0 and the first saving time is 0, so a saving member's first step is saved."""
+        time sums and the save counters restart at 0 and the first saving time is 0, so a saving member's first step is saved.
+        truth None | dict(T=[B,S,H,W], t=[B,S], n=[B] or None), S <= score_capacity: the later snapshots of each member's
+        simulation and their simulated times (needs score_capacity > 0); the scores restart: rows NaN, counters 0.  With
+        scoring on and no truth nothing is ever scored."""
         T0 = torch.as_tensor(T0)
         if T0.dim() != 4 or T0.shape[1] != 1:
             raise ValueError(f"T0 must be [B,1,H,W], got {tuple(T0.shape)}")
@@ -210,6 +270,10 @@ class EnsembleRollout:
             raise ValueError("t_avg_start needs EnsembleRollout(..., profiles=True)")
         if save_every is not None and not self.save_capacity:
             raise ValueError("save_every needs EnsembleRollout(..., save_capacity=S) with S > 0")
+        if truth is not None:
+            if not self.score_capacity:
+                raise ValueError("truth needs EnsembleRollout(..., score_capacity=S) with S > 0")
+            truth = check_truth(truth, B, H, W, self.score_capacity)
         tas = broadcast_member_value(t_avg_start, B, "t_avg_start")
         sev = broadcast_member_value(save_every, B, "save_every")           # 0 = never
         dev = self.device
@@ -231,6 +295,15 @@ class EnsembleRollout:
             x["t_avg_start"].copy_(tas); x["save_every"].copy_(sev)
             for k in ("acc", "weight", "count", "next_save", "saved", "missed"):
                 x[k].zero_()
+        sc = self._sc
+        if sc is not None:
+            sc["truth"].zero_(); sc["truth_t"].fill_(float("inf")); sc["n"].zero_()
+            if truth is not None:
+                S = truth[0].shape[1]
+                sc["truth"][:, :S].copy_(truth[0]); sc["truth_t"][:, :S].copy_(truth[1]); sc["n"].copy_(truth[2])
+            for k in ("next", "scored", "skipped"):
+                sc[k].zero_()
+            sc["table"].fill_(float("nan")); sc["prof"].fill_(float("nan"))
         g = self._g
         if g is None:
             nblk = L.call("mc_rollout_blocks", H, W)
@@ -276,6 +349,11 @@ class EnsembleRollout:
                    L.ptr(x["weight"]), L.ptr(x["count"]), st)
         L.call("mc_rollout_step", L.ptr(uu), L.ptr(vv), uvs, L.ptr(g["scaler"]), L.ptr(s["T"]), L.ptr(g["raq"]),
                L.ptr(g["xc"]), L.ptr(g["yc"]), L.ptr(g["dt"]), L.ptr(g["flags"]), B, H, W, L.ptr(g["Tn"]), L.ptr(g["part"]), st)
+        if self.score_capacity:                                 # T_next is written, t is still the old clock
+            sc = self._sc
+            L.call("mc_score_rollout", L.ptr(s["T"]), L.ptr(g["Tn"]), L.ptr(s["t"]), L.ptr(g["dt"]), L.ptr(g["flags"]), L.ptr(s["t_end"]),
+                   L.ptr(sc["truth"]), L.ptr(sc["truth_t"]), L.ptr(sc["n"]), self.score_capacity, B, H, W, L.ptr(sc["next"]),
+                   L.ptr(sc["scored"]), L.ptr(sc["skipped"]), L.ptr(sc["table"]), L.ptr(sc["prof"]), st)
         L.call("mc_rollout_finalize", L.ptr(g["part"]), L.ptr(g["dt"]), L.ptr(g["flags"]), L.ptr(s["t_end"]), L.ptr(s["t"]),
                L.ptr(s["steps"]), L.ptr(g["cursor"]), L.ptr(g["hist"]), HIST_CHUNK, B, H, W, st)
         if self.save_capacity:                                  # the new clock and the field just written
@@ -292,6 +370,7 @@ class EnsembleRollout:
         s, g = self._s, self._g
         keep = {k: s[k].clone() for k in ("T", "t", "steps")}
         xkeep = {k: v.clone() for k, v in self._x.items()} if self._x is not None else {}
+        sckeep = {k: self._sc[k].clone() for k in self.SCORE_KEYS} if self._sc is not None else {}
         self._set_cursor(0)
         side = torch.cuda.Stream(device=self.device)
         side.wait_stream(torch.cuda.current_stream())
@@ -303,6 +382,8 @@ class EnsembleRollout:
             s[k].copy_(v)
         for k, v in xkeep.items():                              # ... and their statistics
             self._x[k].copy_(v)
+        for k, v in sckeep.items():                             # ... and their scores
+            self._sc[k].copy_(v)
         g["graph"] = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g["graph"]):
             self._one_step()
@@ -315,8 +396,9 @@ class EnsembleRollout:
         returns them; `profiles` (None, or names, acc [B,4,H], weight [B], count [B], mean = acc / weight where weight > 0
         else 0, last [B,4,H]: the profile of the state the last step started from) and `timed` (None, or T [B,S,H,W],
         t [B,S], count [B], missed [B]: the fields saved during THIS run at each member's saving times, slots from count[b]
-        on are stale and their t is NaN; the next saving time carries over to the next run).  Nothing here waits for the
-        device."""
+        on are stale and their t is NaN; the next saving time carries over to the next run) and `score` (None, or names =
+        SCORE_NAMES, table [B,S,8], prof [B,S,2,H] = the row means of prediction and truth, scored [B], skipped [B], next [B]:
+        cumulative since reset(), rows not scored yet are NaN).  Nothing here waits for the device."""
         if self._g is None or self._s is None:
             raise RuntimeError("call reset() first (load_state() alone carries no grid and no parameters)")
         n_steps, every = int(n_steps), int(snapshot_every)
@@ -350,16 +432,20 @@ class EnsembleRollout:
                 done += chunk
             u, v, p = g["out"]
             sv = g["scaler"].view(B, 1, 1, 1)
-            prof = timed = None
+            prof = timed = score = None
             if self.profiles:
                 acc, wt = x["acc"].clone(), x["weight"].clone()
                 mean = torch.where(wt.view(B, 1, 1) > 0, acc / wt.view(B, 1, 1), torch.zeros_like(acc))
                 prof = dict(names=PROFILE_NAMES, acc=acc, weight=wt, count=x["count"].clone(), mean=mean, last=x["last"].clone())
             if self.save_capacity:
                 timed = dict(T=x["snaps"].clone(), t=x["snap_t"].clone(), count=x["saved"].clone(), missed=x["missed"].clone())
+            if self.score_capacity:
+                sc = self._sc
+                score = dict(names=SCORE_NAMES, table=sc["table"].clone(), prof=sc["prof"].clone(), scored=sc["scored"].clone(),
+                             skipped=sc["skipped"].clone(), next=sc["next"].clone())
             return dict(T=s["T"].clone(), t=s["t"].clone(), steps=s["steps"].clone(), hist=hist, names=HIST_NAMES,
                         snapshots=snaps, u=u.unsqueeze(1) * sv, v=v.unsqueeze(1) * sv,
-                        p=p.reshape(B, 1, H, W) if p is not None else None, profiles=prof, timed=timed)
+                        p=p.reshape(B, 1, H, W) if p is not None else None, profiles=prof, timed=timed, score=score)
 
 
 # --------------------------------------------------------------------------------------------------
@@ -383,6 +469,9 @@ def build_arg_parser():
     p.add_argument("--t_avg_start", type=float, default=None, help="simulated time from which the profiles are averaged")
     p.add_argument("--save_every", type=float, default=None, help="simulated time between two saved fields of a member")
     p.add_argument("--save_capacity", type=int, default=0, help="saved fields per member -> timed_snapshots.npz")
+    p.add_argument("--truth", type=str, default=None,
+                   help=".npz with T [B,S,H,W], t [B,S] and optionally n [B]: snapshots the members are scored against -> scores.npz")
+    p.add_argument("--score_capacity", type=int, default=0, help="scored snapshots per member (default: what --truth holds)")
     p.add_argument("--out", type=str, required=True)
     p.add_argument("--synthetic", type=int, nargs=3, metavar=("B", "H", "W"), default=None,
                    help="seeded synthetic grid and initial fields instead of --init")
@@ -426,12 +515,20 @@ def main(argv=None):
             raise SystemExit(f"{a.init} holds {T0.shape[0]} initial fields, {a.params} holds {B} members")
     else:
         raise SystemExit("give --synthetic B H W or --init FILE")
+    truth = None
+    if a.truth:
+        z = np.load(a.truth)
+        truth = dict(T=np.asarray(z["T"], dtype=np.float32), t=np.asarray(z["t"], dtype=np.float64),
+                     n=z["n"] if "n" in z.files else None)
+    elif a.score_capacity:
+        raise SystemExit("--score_capacity needs --truth FILE.npz")
     dev = torch.device(a.device)
     L.load()
     ro = EnsembleRollout(build_stokes(a, dev), dev, CN_max=a.CN_max, precision=a.precision, use_graph=bool(a.graph),
-                         profiles=bool(a.profiles), save_capacity=a.save_capacity)
+                         profiles=bool(a.profiles), save_capacity=a.save_capacity,
+                         score_capacity=a.score_capacity or (truth["T"].shape[1] if truth is not None else 0))
     ro.reset(torch.from_numpy(T0), torch.from_numpy(xc), torch.from_numpy(yc), torch.from_numpy(ycc), paras[:, 0], paras[:, 1],
-             paras[:, 2], normalise_params(paras), t_end=a.t_end, t_avg_start=a.t_avg_start, save_every=a.save_every)
+             paras[:, 2], normalise_params(paras), t_end=a.t_end, t_avg_start=a.t_avg_start, save_every=a.save_every, truth=truth)
     out = ro.run(a.steps, snapshot_every=a.snapshot_every)
     os.makedirs(a.out, exist_ok=True)
     hist = out["hist"].cpu().numpy()
@@ -452,6 +549,11 @@ def main(argv=None):
         tm = {k: v.cpu().numpy() for k, v in out["timed"].items()}
         np.savez(os.path.join(a.out, "timed_snapshots.npz"), **tm)
         summary["timed"] = dict(count=tm["count"].tolist(), missed=tm["missed"].tolist())
+    if out["score"] is not None:
+        from .evaluate import summarise_rollout
+        sc = {k: (list(v) if k == "names" else v.cpu().numpy()) for k, v in out["score"].items()}
+        np.savez(os.path.join(a.out, "scores.npz"), **sc)
+        summary["score"] = summarise_rollout(sc)
     line = json.dumps(summary)
     with open(os.path.join(a.out, "summary.json"), "w") as fh:
         fh.write(line + "\n")
