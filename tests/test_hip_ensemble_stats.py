@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import ensemble_stats_ref as E
+import eval_seams as S
 from test_hip_rollout import CN, SIZES, Guarded, bits, case
 
 pytestmark = pytest.mark.gpu
@@ -15,6 +16,10 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 A0, W0, N0 = 7.5, 3.25, 11           # non-zero prefill of acc, wsum, nacc
 F64, I32 = torch.float64, torch.int32
+# tests/eval_seams.py: a second member of a finalize wave and a second block of the per-member kernels; the row widths and
+# heights at which the scoring kernels change path (the profiles are the row means those kernels restate)
+MEMBER_SIZES = SIZES + S.MEMBER_SHAPES
+PROFILE_SIZES = MEMBER_SIZES + S.WIDTH_SHAPES + S.CHUNK_SHAPES
 
 
 class Profiles:
@@ -67,7 +72,7 @@ def reference(B, H, W):
     return E.profiles(c["u"].cpu().numpy(), c["v"].cpu().numpy(), c["vs"].cpu().numpy(), c["T"].cpu().numpy())
 
 
-@pytest.mark.parametrize("B,H,W", SIZES)
+@pytest.mark.parametrize("B,H,W", PROFILE_SIZES)
 def test_profiles_against_numpy_f64(B, H, W):
     got = free_profiles(B, H, W)["prof"].numpy()
     want, mag = reference(B, H, W)
@@ -81,7 +86,10 @@ def test_profiles_against_numpy_f64(B, H, W):
             print(f"member {b} {('T', 'u2', 'v2', 'vT')[q]} row {i}: got {got[b, q, i]!r} want {want[b, q, i]!r} |diff| {d[i]:.3e} "
                   f"gate {gate[b, q, i]:.3e}")
             worst = max(worst, float((d / np.maximum(gate[b, q], 1e-300)).max()))
+    print(f"worst |got - want| / gate: {worst:.3e}")
     assert (np.abs(got - want) <= gate).all(), worst
+    for m in S.named_members(B):                               # a row of block b * H / 4 far from block 0, by name
+        assert (np.abs(got[m] - want[m]) <= gate[m]).all() and not np.array_equal(got[m], got[m - 4]), m
     assert (got[B - 1, 1:3] == 0).all() and (got[B - 1, 3] == 0).all()             # the member at rest
     assert (got[:B - 1, 1:3] > 0).all()
     # cross-check: the mean over the rows of the T profile is the all-cell mean of T (the history's T_mean convention)
@@ -107,7 +115,7 @@ def test_profiles_do_not_depend_on_the_batch(B, H, W):
     assert torch.equal(bits(rev["wsum"].flip(0)), bits(got["wsum"]))
 
 
-@pytest.mark.parametrize("B,H,W", SIZES)
+@pytest.mark.parametrize("B,H,W", MEMBER_SIZES)
 def test_time_weights(B, H, W):
     c = case(B, H, W)
     t0 = [1.0 + 0.125 * b for b in range(B)]
@@ -125,36 +133,54 @@ def test_time_weights(B, H, W):
     assert got["wsum"].numpy().tolist() == want and got["nacc"].tolist() == [1] * B
     pr = got["prof"].numpy()
     assert np.array_equal(got["acc"].numpy(), np.asarray(want)[:, None, None] * pr)
+    for m in S.named_members(B):                               # every member its own clock, step and averaging start
+        assert float(got["wsum"][m]) == want[m] and int(got["nacc"][m]) == 1 and want[m] != want[m - 4], m
+        assert np.array_equal(got["acc"][m].numpy(), want[m] * pr[m]) and float(got["t"][m]) == 1.0 + 0.125 * m, m
     # at the end of the step and beyond it: nothing is accumulated, the profile is still written
     q = Profiles(c, list(range(B)), t0=t0, prefill=(A0, W0, N0))
-    got = q.call(tas=[t0[0] + d[0]] + [5.0] * (B - 1))
+    got = q.call(tas=[t0[0] + d[0]] + [max(5.0, t0[b] + 2.0) for b in range(1, B)])      # (5.0, or beyond a later clock)
     assert (got["acc"] == A0).all() and (got["wsum"] == W0).all() and (got["nacc"] == N0).all()
     assert torch.equal(bits(got["prof"]), bits(free_profiles(B, H, W)["prof"]))
 
 
-@pytest.mark.parametrize("B,H,W", SIZES)
+@pytest.mark.parametrize("B,H,W", MEMBER_SIZES)
 def test_frozen_and_landing_members(B, H, W):
     c = case(B, H, W)
     d = free_profiles(B, H, W)["dt"].numpy()
+    role = S.roles(B, last=S.FROZEN)                           # member 0 frozen, member 1 landing; in the larger batches also 4 / 5,
+    frozen = [b for b in range(B) if role[b] == S.FROZEN]      # ... 253 landing, 255 and the one member of block 1 frozen
+    landing = [b for b in range(B) if role[b] == S.LAND]
     t0 = [1.0] * B
     t_end = [float("inf")] * B
-    t_end[0] = 0.5                                             # member 0 is past its stopping time
-    t_end[1] = 1.0 + 0.3 * float(d[1])                         # member 1 crosses it within this step
+    for b in frozen:
+        t_end[b] = 0.5                                         # past its stopping time
+    for b in landing:
+        t_end[b] = 1.0 + 0.3 * float(d[b])                     # crosses it within this step
     p = Profiles(c, list(range(B)), t0=t0, t_end=t_end, prefill=(A0, W0, N0))
     got = p.call(tas=[0.0] * B)
-    assert got["flags"].tolist() == [0, 2] + [1] * (B - 2)
-    # frozen: weight 0, its sums are bit-unchanged; its profile is still that of its field
-    assert (got["acc"][0] == A0).all() and float(got["wsum"][0]) == W0 and int(got["nacc"][0]) == N0
+    assert got["flags"].tolist() == role and role[:2] == [0, 2]
     assert torch.equal(bits(got["prof"]), bits(free_profiles(B, H, W)["prof"]))
-    # landing: the f64 remainder t_end - t
-    short = np.float64(t_end[1]) - np.float64(1.0)
-    assert 0 < short < d[1] and float(got["dt"][1]) == short
-    assert float(got["wsum"][1]) == W0 + short and int(got["nacc"][1]) == N0 + 1
     pr = got["prof"].numpy()
-    assert np.array_equal(got["acc"][1].numpy(), A0 + short * pr[1])
+    for b in frozen:
+        # frozen: weight 0, its sums are bit-unchanged; its profile is still that of its field
+        assert (got["acc"][b] == A0).all() and float(got["wsum"][b]) == W0 and int(got["nacc"][b]) == N0, b
+    for b in landing:
+        # landing: the f64 remainder t_end - t
+        short = np.float64(t_end[b]) - np.float64(1.0)
+        assert 0 < short < d[b] and float(got["dt"][b]) == short, b
+        assert float(got["wsum"][b]) == W0 + short and int(got["nacc"][b]) == N0 + 1, b
+        assert np.array_equal(got["acc"][b].numpy(), A0 + short * pr[b]), b
     for b in range(2, B):
-        assert float(got["wsum"][b]) == W0 + d[b] and int(got["nacc"][b]) == N0 + 1
-        assert np.array_equal(got["acc"][b].numpy(), A0 + d[b] * pr[b])
+        if role[b] != S.STEP:
+            continue
+        assert float(got["wsum"][b]) == W0 + d[b] and int(got["nacc"][b]) == N0 + 1, b
+        assert np.array_equal(got["acc"][b].numpy(), A0 + d[b] * pr[b]), b
+    if B > 5:                                                  # by name: both sides of index 4
+        assert got["flags"][3:6].tolist() == [1, 0, 2] and got["nacc"][3:6].tolist() == [N0 + 1, N0, N0 + 1]
+        assert float(got["wsum"][4]) == W0 and float(got["wsum"][5]) == W0 + (np.float64(t_end[5]) - 1.0)
+    if B > 256:                                                # ... and of index 256
+        assert got["flags"][253:].tolist() == [2, 1, 0, 0] and got["nacc"][253:].tolist() == [N0 + 1, N0 + 1, N0, N0]
+        assert float(got["wsum"][254]) == W0 + d[254] and float(got["wsum"][256]) == W0 and (got["acc"][256] == A0).all()
 
 
 @pytest.mark.parametrize("B,H,W", SIZES)
@@ -175,19 +201,22 @@ def test_accumulation_over_two_calls(B, H, W):
     assert np.array_equal(got["wsum"].numpy(), (W0 + w1) + w2) and got["nacc"].tolist() == [N0 + 2] * B
 
 
-@pytest.mark.parametrize("B,H,W", SIZES)
+@pytest.mark.parametrize("B,H,W", MEMBER_SIZES)
 def test_snapshot_rule(B, H, W):
     from pbml_mantle_convection_amd import _lib as L
     c = case(B, H, W)
-    idx = [k % B for k in range(4)]                            # four members at every size
-    n, cap, reps = 4, 2, 3
-    d = [1e-3, 2e-3, 1.5e-3, 1e-3]
-    every = [1.5 * d[0], 0.5 * d[1], 0.0, 0.5 * d[3]]          # steps 1 and 3; every step; never; (frozen)
-    flags = [E.STEP, E.LAND, E.STEP, E.FROZEN]
+    n, cap, reps = max(4, B), 2, 3                             # four members at every size; every member of the larger batches
+    idx = [k % B for k in range(n)]
+    # member m follows pattern m % 4 on a clock of its own: step d[m], saving time every[m]
+    d = [(1e-3, 2e-3, 1.5e-3, 1e-3)[m % 4] * (1.0 + 0.25 * (m // 4)) for m in range(n)]
+    every = [(1.5, 0.5, 0.0, 0.5)[m % 4] * d[m] for m in range(n)]       # steps 1 and 3; every step; never; (frozen)
+    flags = [(E.STEP, E.LAND, E.STEP, E.FROZEN)[m % 4] for m in range(n)]
+    assert d[:4] == [1e-3, 2e-3, 1.5e-3, 1e-3] and len(set(zip(d, every, flags))) == n
     clocks = [[(k + 1) * d[m] for k in range(reps)] for m in range(n)]
     # the host arithmetic of these conditions, before anything runs on the device
     rule = [E.save_rule(clocks[m], [flags[m]] * reps, every[m], cap) for m in range(n)]
-    assert [r[0] for r in rule] == [[0, 2], [0, 1], [], []] and [r[1] for r in rule] == [[], [2], [], []]
+    assert [r[0] for r in rule] == [([0, 2], [0, 1], [], [])[m % 4] for m in range(n)]
+    assert [r[1] for r in rule] == [([], [2], [], [])[m % 4] for m in range(n)]
     g = dict(t=Guarded((n,), F64, float("nan")), flags=Guarded((n,), I32, -1), every=Guarded((n,), F64, 0.0),
              nxt=Guarded((n,), F64, 0.0), count=Guarded((n,), I32, 0), missed=Guarded((n,), I32, 0), slot=Guarded((n,), I32, -7),
              snaps=Guarded((n, cap, H, W), torch.float32, float("nan")), snap_t=Guarded((n, cap), F64, float("nan")))
@@ -204,9 +233,18 @@ def test_snapshot_rule(B, H, W):
     for k, b in g.items():
         assert b.intact(), f"{k}: a kernel wrote outside its buffer"
     got = {k: b.t.cpu().clone() for k, b in g.items()}
-    assert slots == [[0, 0, -1, -1], [-1, 1, -1, -1], [1, -1, -1, -1]]
-    assert got["count"].tolist() == [2, 2, 0, 0] and got["missed"].tolist() == [0, 1, 0, 0]
+    assert [s_[:4] for s_ in slots] == [[0, 0, -1, -1], [-1, 1, -1, -1], [1, -1, -1, -1]]
+    assert slots == [[(0, 0, -1, -1)[m % 4] for m in range(n)], [(-1, 1, -1, -1)[m % 4] for m in range(n)],
+                     [(1, -1, -1, -1)[m % 4] for m in range(n)]]
+    assert got["count"].tolist() == [(2, 2, 0, 0)[m % 4] for m in range(n)]
+    assert got["missed"].tolist() == [(0, 1, 0, 0)[m % 4] for m in range(n)]
     assert got["nxt"].tolist() == [float(r[2]) for r in rule]
+    for m in S.named_members(n):                               # by name: the second member of a wave; thread 255 of block 0, thread 0 of block 1
+        assert [s_[m] for s_ in slots] == [[0, -1, 1], [0, 1, -1], [-1, -1, -1], [-1, -1, -1]][m % 4], m
+        assert int(got["count"][m]) == (2, 2, 0, 0)[m % 4] and float(got["nxt"][m]) == float(rule[m][2]), m
+        assert m % 4 > 1 or float(got["nxt"][m]) != float(got["nxt"][m - 4]), m                   # (a member that saves: its own clock)
+    if n > 256:
+        assert got["snap_t"][256].tolist() == [clocks[256][0], clocks[256][2]] and got["count"][255:].tolist() == [0, 2]
     for m in range(n):
         for sl in range(cap):
             if sl < len(rule[m][0]):

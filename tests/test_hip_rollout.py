@@ -8,8 +8,9 @@ import numpy as np
 import pytest
 import torch
 
-import fields
+import eval_seams as S
 import step_cases as Sc
+from eval_seams import grid  # noqa: F401  (the uniform grid; test_hip_series_score imports it from here)
 
 pytestmark = pytest.mark.gpu
 
@@ -25,6 +26,8 @@ class Stretched(int):
 # partials of a member take k_rollout_finalize through its second lane pass
 SIZES = [(3, 5, 6), (2, 9, 70), (4, 33, 130), (2, 130, 260)]
 CASES = SIZES + [pytest.param(4, 33, Stretched(130), id="4-33-130-stretched")]      # and the stretched grid at an existing size
+# more members than k_rollout_finalize has waves, and more than one block of the per-member kernels (tests/eval_seams.py)
+MEMBER_CASES = CASES + S.MEMBER_SHAPES
 CN = 0.1
 
 
@@ -47,12 +50,6 @@ class Guarded:
         return bool((self.raw[:self.g] == SENTINEL).all()) and bool((self.raw[self.g + self.nbytes:] == SENTINEL).all())
 
 
-def grid(H, W):
-    xs = np.concatenate(([0.0], (np.arange(W - 2) + 0.5) * 4.0 / (W - 2), [4.0]))
-    ys = np.concatenate(([0.0], (np.arange(H - 2) + 0.5) * 1.0 / (H - 2), [1.0]))
-    return (np.broadcast_to(xs[None, :], (H, W)).astype(np.float32).copy(), np.broadcast_to(ys[:, None], (H, W)).astype(np.float32).copy())
-
-
 def dev(a, dtype=torch.float32):
     return torch.from_numpy(np.ascontiguousarray(a)).to(dtype).to(DEV).contiguous()
 
@@ -64,15 +61,12 @@ def case(B, H, W):
 @functools.lru_cache(maxsize=None)
 def _case(B, H, W, stretched):
     """Members with different fields, different vel_scale and different RaQ; the LAST member is at rest (u = v = 0)."""
-    seed = 100 * B + H
-    u = fields.smooth_field(B, H, W, seed + 1) * 2000.0
-    v = fields.smooth_field(B, H, W, seed + 2) * 2000.0
-    u[B - 1] = 0.0
-    v[B - 1] = 0.0
+    u, v, T = S.rollout_fields(B, H, W)
+    vs, raq = S.member_scalars(B)
     xc, yc = Sc.grid_stretched(H, W) if stretched else grid(H, W)
     walls = tuple(a.astype(np.float32) for a in Sc.with_walls(xc, yc))            # what the kernels substitute, for the checks
-    return dict(B=B, H=H, W=W, stretched=stretched, grid=walls, u=dev(u), v=dev(v), T=dev(fields.temperature_field(B, H, W, seed + 3)),
-                vs=dev(np.array([0.5, 1.7, 3.0, 0.9])[:B]), raq=dev(np.array([1.5, 2.5, 4.0, 9.0])[:B]), xc=dev(xc), yc=dev(yc))
+    return dict(B=B, H=H, W=W, stretched=stretched, grid=walls, u=dev(u), v=dev(v), T=dev(T), vs=dev(vs), raq=dev(raq), xc=dev(xc),
+                yc=dev(yc))
 
 
 def adnet(c, idx, dt=None):
@@ -152,7 +146,7 @@ def bits(a):
     return a.contiguous().view(torch.int64 if a.dtype == torch.float64 else torch.int32)
 
 
-@pytest.mark.parametrize("B,H,W", CASES)
+@pytest.mark.parametrize("B,H,W", MEMBER_CASES)
 def test_cfl_step_is_per_member(B, H, W):
     ref, got = reference(B, H, W), free_run(B, H, W)
     dt = got["dt"]
@@ -171,9 +165,13 @@ def test_cfl_step_is_per_member(B, H, W):
     assert got["flags"].tolist() == [1] * B
     assert got["hist"][0, :, 1].tolist() == dt.tolist() and got["hist"][0, :, 0].tolist() == dt.tolist()
     assert got["t"].tolist() == dt.tolist() and got["steps"].tolist() == [1] * B and got["cursor"].tolist() == [1]
+    for m in S.named_members(B):                               # a wave's second member; the last thread of block 0, the first of block 1
+        assert float(dt[m]) == float(ref["dt"][m]) and int(got["flags"][m]) == 1 and int(got["steps"][m]) == 1, m
+        assert float(got["t"][m]) == float(dt[m]) and got["hist"][0, m, :2].tolist() == [float(dt[m])] * 2, m
+        assert float(dt[m]) != float(dt[m - 4]) and float(dt[m]) != float(dt[m - 1]), m
 
 
-@pytest.mark.parametrize("B,H,W", CASES)
+@pytest.mark.parametrize("B,H,W", MEMBER_CASES)
 def test_step_equals_adnet_on_each_member_alone(B, H, W):
     ref, got = reference(B, H, W), free_run(B, H, W)
     assert not torch.isnan(got["Tn"]).any()
@@ -181,41 +179,62 @@ def test_step_equals_adnet_on_each_member_alone(B, H, W):
         assert torch.equal(bits(got["Tn"][b]), bits(ref["Tn"][b])), f"member {b}: {(got['Tn'][b] - ref['Tn'][b]).abs().max()}"
     assert (got["Tn"][:, 0] == 1).all() and (got["Tn"][:, -1] == 0).all()
     assert torch.equal(got["Tn"][:, :, 0], got["Tn"][:, :, 1]) and torch.equal(got["Tn"][:, :, -1], got["Tn"][:, :, -2])
+    for m in S.named_members(B):
+        assert torch.equal(bits(got["Tn"][m]), bits(ref["Tn"][m])) and not torch.equal(got["Tn"][m], got["Tn"][m - 4]), m
 
 
-@pytest.mark.parametrize("B,H,W", CASES)
+@pytest.mark.parametrize("B,H,W", MEMBER_CASES)
 def test_stopping_rule(B, H, W):
     c, ref = case(B, H, W), reference(B, H, W)
     dts = ref["dt"].double()
+    role = S.roles(B, last=S.LAND)                             # member 0 frozen, member 1 landing; in the larger batches also 4 / 5
+    frozen, landing = [b for b in range(B) if role[b] == S.FROZEN], [b for b in range(B) if role[b] == S.LAND]
+    assert frozen[0] == 0 and landing[0] == 1 and (B <= 5 or (4 in frozen and 5 in landing))
+    assert B <= 256 or (255 in frozen and 256 in landing)
     t0 = [1.0] * B
     t_end = [float("inf")] * B
-    t_end[0] = 0.5                                             # member 0 is past its stopping time
-    t_end[1] = 1.0 + 0.3 * float(dts[1])                       # member 1 crosses it within this step
+    for b in frozen:
+        t_end[b] = 0.5                                         # past its stopping time
+    for b in landing:
+        t_end[b] = 1.0 + 0.3 * float(dts[b])                   # crosses it within this step, every member at a time of its own
     steps0 = [5 + b for b in range(B)]
     got = rollout(c, list(range(B)), t0=t0, t_end=t_end, steps0=steps0)
-    # frozen: T copied, clock and count untouched, dt = 0 in the history row
-    assert torch.equal(bits(got["Tn"][0]), bits(c["T"][0].cpu()))
-    assert float(got["t"][0]) == 1.0 and int(got["steps"][0]) == 5 and int(got["flags"][0]) == 0
-    assert float(got["hist"][0, 0, 1]) == 0.0 and float(got["hist"][0, 0, 0]) == 1.0
-    # landing: the clock is SET to t_end, the row holds t_end - t_before, the field took that (f32) step
-    assert float(got["t"][1]) == t_end[1] and int(got["flags"][1]) == 2 and int(got["steps"][1]) == 7
-    short = t_end[1] - 1.0
-    assert float(got["hist"][0, 1, 1]) == short and float(got["hist"][0, 1, 0]) == t_end[1]
-    assert 0 < short < float(dts[1])
-    _, Tn1 = adnet(c, [1], dt=np.float32(short))
-    assert torch.equal(bits(got["Tn"][1]), bits(Tn1[0]))
-    assert not torch.equal(got["Tn"][1], ref["Tn"][1])
+    assert got["flags"].tolist() == role
+    for b in frozen:
+        # frozen: T copied, clock and count untouched, dt = 0 in the history row
+        assert torch.equal(bits(got["Tn"][b]), bits(c["T"][b].cpu())), b
+        assert float(got["t"][b]) == 1.0 and int(got["steps"][b]) == 5 + b and int(got["flags"][b]) == 0, b
+        assert float(got["hist"][0, b, 1]) == 0.0 and float(got["hist"][0, b, 0]) == 1.0, b
+    for b in landing:
+        # landing: the clock is SET to t_end, the row holds t_end - t_before, the field took that (f32) step
+        assert float(got["t"][b]) == t_end[b] and int(got["flags"][b]) == 2 and int(got["steps"][b]) == 6 + b, b
+        short = t_end[b] - 1.0
+        assert float(got["hist"][0, b, 1]) == short and float(got["hist"][0, b, 0]) == t_end[b], b
+        assert 0 < short < float(dts[b]), b
+        _, Tn1 = adnet(c, [b], dt=np.float32(short))
+        assert torch.equal(bits(got["Tn"][b]), bits(Tn1[0])), b
+        assert not torch.equal(got["Tn"][b], ref["Tn"][b]), b
     # the others step as if alone
     for b in range(2, B):
-        assert torch.equal(bits(got["Tn"][b]), bits(ref["Tn"][b]))
-        assert float(got["t"][b]) == 1.0 + float(dts[b]) and int(got["steps"][b]) == 6 + b
+        if role[b] != S.STEP:
+            continue
+        assert torch.equal(bits(got["Tn"][b]), bits(ref["Tn"][b])), b
+        assert float(got["t"][b]) == 1.0 + float(dts[b]) and int(got["steps"][b]) == 6 + b, b
+    if B > 5:                                                  # both sides of the second member of a wave, by name
+        assert got["flags"][3:6].tolist() == [1, 0, 2] and got["steps"][3:6].tolist() == [9, 9, 11]
+        assert got["t"][4:6].tolist() == [1.0, t_end[5]]
+    if B > 256:                                                # both sides of the block boundary of the per-member kernels
+        assert got["flags"][252:].tolist() == [1, 2, 1, 0, 2] and got["steps"][252:].tolist() == [258, 259, 260, 260, 262]
+        assert got["t"][253:].tolist() == [t_end[253], 1.0 + float(dts[254]), 1.0, t_end[256]]
+        assert float(got["hist"][0, 256, 1]) == t_end[256] - 1.0 and float(got["dt"][256]) == t_end[256] - 1.0
     # a member that has landed is inactive from then on
-    again = rollout(c, [1], t0=[t_end[1]], t_end=[t_end[1]], steps0=[7])
-    assert int(again["flags"][0]) == 0 and float(again["dt"][0]) == 0.0 and float(again["t"][0]) == t_end[1]
-    assert torch.equal(bits(again["Tn"][0]), bits(c["T"][1].cpu()))
+    for b in landing:
+        again = rollout(c, [b], t0=[t_end[b]], t_end=[t_end[b]], steps0=[7])
+        assert int(again["flags"][0]) == 0 and float(again["dt"][0]) == 0.0 and float(again["t"][0]) == t_end[b], b
+        assert torch.equal(bits(again["Tn"][0]), bits(c["T"][b].cpu())), b
 
 
-@pytest.mark.parametrize("B,H,W", CASES)
+@pytest.mark.parametrize("B,H,W", MEMBER_CASES)
 def test_diagnostics_against_numpy_f64(B, H, W):
     c, got = case(B, H, W), free_run(B, H, W)
     Tn = got["Tn"].double().numpy()
@@ -223,22 +242,15 @@ def test_diagnostics_against_numpy_f64(B, H, W):
     yc = c["grid"][1].astype(np.float64)
     h = got["hist"][0].numpy()
     assert np.isfinite(h).all()
-    for b in range(B):
-        terms = {2: Tn[b].ravel(),
-                 3: ((s[b] * u[b]) ** 2 + (s[b] * v[b]) ** 2).ravel(),
-                 4: (Tn[b, 0, 1:-1] - Tn[b, 1, 1:-1]) / (yc[1, 1:-1] - 0.0),
-                 5: (Tn[b, H - 2, 1:-1] - Tn[b, H - 1, 1:-1]) / (1.0 - yc[H - 2, 1:-1])}
-        for col, tm in terms.items():
-            val = h[b, col] ** 2 if col == 3 else h[b, col]          # v_rms: the gate is on the mean square it is the root of
-            want, gate = tm.sum() / tm.size, 1e-6 * np.abs(tm).sum() / tm.size
-            print(f"member {b} column {col}: got {val!r} want {want!r} |diff| {abs(val - want):.3e} gate {gate:.3e}")
-            assert abs(val - want) <= gate, (b, col, val, want, gate)
-        assert h[b, 6] == Tn[b].min() and h[b, 7] == Tn[b].max()                  # exact
+    worst = [S.diagnostics_check(h[b], Tn[b], u[b], v[b], s[b], yc, b) for b in range(B)]      # sums within 1e-6 sum|terms|; min, max exact
+    print(f"worst |got - want| / gate over {B} members: {max(worst):.3e} (member {int(np.argmax(worst))})")
+    for m in S.named_members(B):
+        assert worst[m] <= 1.0 and h[m, 6] == Tn[m].min() and h[m, 7] == Tn[m].max() and h[m, 2] != h[m - 4, 2], m
     assert h[B - 1, 3] == 0.0                                                      # the member at rest
     assert (h[:B - 1, 3] > 0).all()
 
 
-@pytest.mark.parametrize("B,H,W", CASES)
+@pytest.mark.parametrize("B,H,W", MEMBER_CASES)
 def test_diagnostics_do_not_depend_on_the_batch(B, H, W):
     c, got = case(B, H, W), free_run(B, H, W)
     twice = rollout(c, list(range(B)))

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+import eval_seams as S
 import fields
 import rollout_score_ref as R
 from test_hip_rollout import CN, SIZES, Guarded, bits, case
@@ -18,6 +19,10 @@ DEV = "cuda:0"
 F32, F64, I32 = torch.float32, torch.float64, torch.int32
 NAN, INF = float("nan"), float("inf")
 K0, S0 = 5, 7                         # non-zero prefill of scored, skipped
+# tests/eval_seams.py: widths at which the lanes of rs_walk_row split between its two loops or take the main loop twice, heights
+# of exactly one chunk and of one chunk and a row; batches with more than one block and more than four members
+ROW_SIZES = SIZES + S.WIDTH_SHAPES + S.CHUNK_SHAPES
+MEMBER_SIZES = SIZES + S.MEMBER_SHAPES
 
 
 @functools.lru_cache(maxsize=None)
@@ -102,6 +107,8 @@ def check(got, want, rows=None):
         d = np.abs(prof[m, k] - want["prof"][m, k])
         i = np.unravel_index(int(np.argmax(d - want["gate_prof"][m, k])), d.shape)
         print(f"member {m} row {k} profiles: worst |diff| {d[i]:.3e} gate {want['gate_prof'][m, k][i]:.3e}")
+    print(f"worst |got - want| / gate: table {S.worst_ratio(table, want['table'], want['gate']):.3e} "
+          f"profiles {S.worst_ratio(prof, want['prof'], want['gate_prof']):.3e}")
     assert R.within(table, want["table"], np.nan_to_num(want["gate"], nan=0.0))
     assert R.within(prof, want["prof"], np.nan_to_num(want["gate_prof"], nan=0.0))
     written = np.zeros(table.shape[:2], bool)
@@ -115,7 +122,7 @@ def clocks(n):
     return [1.0 + 0.125 * m for m in range(n)]
 
 
-@pytest.mark.parametrize("B,H,W", SIZES)
+@pytest.mark.parametrize("B,H,W", ROW_SIZES)
 def test_one_time_inside_the_step(B, H, W):
     s = Scorer(case(B, H, W), list(range(B)), 2, t0=clocks(B))
     assert s.flags.tolist() == [1] * B and (s.dt > 0).all()
@@ -129,7 +136,7 @@ def test_one_time_inside_the_step(B, H, W):
     assert np.isfinite(row).all() and (row[:, 2] > 0).all() and (row[:, 3] >= row[:, 2]).all() and (np.abs(row[:, 4]) <= 1).all()
 
 
-@pytest.mark.parametrize("B,H,W", SIZES)
+@pytest.mark.parametrize("B,H,W", ROW_SIZES)
 def test_three_times_inside_one_step(B, H, W):
     s = Scorer(case(B, H, W), list(range(B)), 4, t0=clocks(B))
     tt = np.stack([s.t0 + f * s.dt for f in (0.25, 0.5, 0.75, 1.25)], 1)
@@ -168,7 +175,7 @@ def test_theta_zero_and_identical_fields(B, H, W):
     assert (got["table"][:, 1, 1] == 0.5).all() and (got["table"][:, 1, 2] > 0).all()
 
 
-@pytest.mark.parametrize("B,H,W", SIZES)
+@pytest.mark.parametrize("B,H,W", ROW_SIZES)
 def test_theta_one_at_the_end_of_a_step_and_on_landing(B, H, W):
     c = case(B, H, W)
     free = Scorer(c, list(range(B)), 1, t0=clocks(B))
@@ -189,27 +196,46 @@ def test_theta_one_at_the_end_of_a_step_and_on_landing(B, H, W):
     check(got, want, rows=[])
 
 
-@pytest.mark.parametrize("B,H,W", SIZES)
+@pytest.mark.parametrize("B,H,W", MEMBER_SIZES)
 def test_late_times_frozen_members_and_counts(B, H, W):
     c = case(B, H, W)
     cap = 3
     t0 = clocks(B)
     t_end = [INF] * B
-    t_end[0] = 0.5                                                                   # member 0 is past its stopping time: frozen
+    pat = [m % 4 for m in range(B)]                                                  # beyond four members the four patterns repeat:
+    for m in range(0, B, 4):
+        t_end[m] = 0.5                                                               # 0, 4, ..., 256 are past their stopping time: frozen
+    if B > 4:
+        free = Scorer(c, list(range(B)), cap, t0=t0)
+        for m in range(7, B, 4):
+            t_end[m] = t0[m] + 0.9 * float(free.dt[m])                               # 7, 11, ..., 255 land inside this step
     s = Scorer(c, list(range(B)), cap, t0=t0, t_end=t_end)
-    assert s.flags.tolist() == [0] + [1] * (B - 1)
-    # member 0: due times, but frozen.  member 1: a time the clock had passed (skipped), then one inside the step.
-    # members 2..: n_truth = 0 (nothing counts) / n_truth = 1 of three due times.
+    assert s.flags.tolist() == [0 if pat[m] == 0 else (2 if (pat[m] == 3 and m > 3) else 1) for m in range(B)]
+    assert s.flags.tolist()[:4] == [0, 1, 1, 1][:B]
+    # pattern 0: due times, but frozen.  pattern 1: a time the clock had passed (skipped), then one inside the step.
+    # patterns 2, 3: n_truth = 0 (nothing counts) / n_truth = 1 of three due times.
     d = np.where(s.dt > 0, s.dt, 1e-6)                                               # (the frozen member's dt is 0)
     tt = np.stack([s.t0 - 0.25, s.t0 + 0.5 * d, s.t0 + 0.75 * d], 1)
-    n = [3, 3, 0, 1][:B]
-    tt[2:, 0] = s.t0[2:] + 0.25 * s.dt[2:]
+    n = [(3, 3, 0, 1)[q] for q in pat]
+    late = np.array([q >= 2 for q in pat])
+    tt[late, 0] = s.t0[late] + 0.25 * s.dt[late]
     got, want = s.truth(truth_fields(B, cap, H, W), tt, n).call()
-    rows = [(1, 1), (1, 2)] + ([(3, 0)] if B > 3 else [])
+    rows = [r for m in range(B) for r in ([(m, 1), (m, 2)] if pat[m] == 1 else ([(m, 0)] if pat[m] == 3 else []))]
+    assert rows[:3] == ([(1, 1), (1, 2)] + ([(3, 0)] if B > 3 else []))[:3]
     check(got, want, rows=rows)
-    assert got["next"].tolist() == [0, 3, 0, 1][:B]
-    assert got["scored"].tolist() == [K0, K0 + 2, K0, K0 + 1][:B] and got["skipped"].tolist() == [S0, S0 + 1, S0, S0][:B]
+    assert got["next"].tolist() == [(0, 3, 0, 1)[q] for q in pat]
+    assert got["scored"].tolist() == [(K0, K0 + 2, K0, K0 + 1)[q] for q in pat] and got["skipped"].tolist() == [(S0, S0 + 1, S0, S0)[q] for q in pat]
     assert bool(torch.isnan(got["table"][0]).all()) and bool(torch.isnan(got["table"][1, 0]).all())      # frozen; the late row
+    if B > 5:                                                                        # by name: a workgroup beyond the first four
+        assert bool(torch.isnan(got["table"][4]).all()) and int(got["scored"][4]) == K0 and int(got["next"][4]) == 0
+        assert int(got["scored"][5]) == K0 + 2 and int(got["skipped"][5]) == S0 + 1 and bool(torch.isfinite(got["table"][5, 1:, :4]).all())
+        assert bool(torch.isnan(got["table"][5, 0]).all()) and float(got["table"][5, 1, 0]) == tt[5, 1] != tt[1, 1]
+    if B > 256:                                                                      # ... the landing 255 and the frozen 256, whose dt and
+        assert int(s.flags[255]) == 2 and int(s.flags[256]) == 0                     # flags thread 0 of block 1 of k_rollout_dt wrote
+        assert int(got["scored"][255]) == K0 + 1 and int(got["next"][255]) == 1 and float(got["table"][255, 0, 0]) == tt[255, 0]
+        assert s.t1[255] == np.float64(t_end[255]) and 0 < s.dt[255] < free.dt[255]  # (the landing step is the shorter one, and
+        assert abs(float(got["table"][255, 0, 1]) - 0.25) < 1e-6                     # theta is taken on its own length)
+        assert bool(torch.isnan(got["table"][256]).all()) and int(got["scored"][256]) == K0 and int(got["skipped"][256]) == S0
 
 
 @pytest.mark.parametrize("B,H,W", SIZES)
@@ -232,7 +258,7 @@ def test_constant_truth_has_no_correlation(B, H, W):
     assert (row[:, 7] == np.float64(np.float32(0.3))).all() and (got["prof"][:, 0, 1] == float(np.float32(0.3))).all()
 
 
-@pytest.mark.parametrize("B,H,W", SIZES)
+@pytest.mark.parametrize("B,H,W", ROW_SIZES + S.MEMBER_SHAPES)
 def test_rows_do_not_depend_on_the_batch(B, H, W):
     c = case(B, H, W)
     T = truth_fields(B, 2, H, W)
@@ -248,5 +274,7 @@ def test_rows_do_not_depend_on_the_batch(B, H, W):
         alone = run([m])                                                             # alone (b = 1) and inside the batch
         assert torch.equal(bits(alone["table"][0]), bits(whole["table"][m])), m
         assert torch.equal(bits(alone["prof"][0]), bits(whole["prof"][m])), m
+    for m in S.named_members(B):
+        assert not torch.equal(whole["table"][m, :, 2:4], whole["table"][m - 4, :, 2:4]), m      # another member, another row
     rev = run(list(range(B))[::-1])                                                  # and on its place in the batch
     assert torch.equal(bits(rev["table"].flip(0)), bits(whole["table"])) and torch.equal(bits(rev["prof"].flip(0)), bits(whole["prof"]))

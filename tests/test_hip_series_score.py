@@ -8,36 +8,28 @@ import numpy as np
 import pytest
 import torch
 
-import fields
+import eval_seams as S
 import series_score_ref as R
 from test_hip_rollout import DEV, Guarded, dev, grid
 
 pytestmark = pytest.mark.gpu
 
 SIZES = [(3, 3, 3), (5, 7, 70), (4, 33, 130)]      # a 1 x 1 interior; a ragged row longer than a wave; several rows a block, 3 waves a row
+# tests/eval_seams.py: heights at which k_series_finalize takes exactly one pass, a second pass of one row, three passes; a
+# field whose gather takes the grid-stride pass
+FINALIZE_SIZES = SIZES + S.SERIES_SHAPES
 F64, I32, F32 = torch.float64, torch.int32, torch.float32
-INV = np.array([1.0 / 1700.0, 1.0 / 260.0], dtype=np.float32)       # two simulations, different velocity scales
+INV = S.INV                                       # two simulations, different velocity scales
 
 
 @functools.lru_cache(maxsize=None)
 def case(N, H, W):
     """A store of N snapshots of two simulations (the second half belongs to simulation 1) and one prediction per snapshot in
     the scaled space: the scaled truth (0.1 to 0.8 in size) plus a smooth error of about 0.1."""
-    seed = 1000 * N + H
-    u = fields.smooth_field(N, H, W, seed + 1) * 2000.0
-    v = fields.smooth_field(N, H, W, seed + 2) * 2000.0
-    T = fields.temperature_field(N, H, W, seed + 3)
-    sim = np.array([0] * (N - N // 2) + [1] * (N // 2), dtype=np.int32)
-    prev = np.full(N, -1, dtype=np.int32)
-    for n in range(1, N):
-        if sim[n] == sim[n - 1]:
-            prev[n] = n - 1
+    f = S.series_fields(N, H, W)
+    u, v, T, sim, prev, pred = f["u"], f["v"], f["T"], f["sim"], f["prev"], f["pred"]
     paras = np.array([[1.5, 1e6, 10.0], [4.0, 1e8, 60.0]])
     nd = np.array([[0.15, 0.0, 0.5], [0.4, 0.51, 0.89]])
-    pred = np.zeros((N, 3, H, W), dtype=np.float32)                  # planes 0, 1 of a 3-channel output: batch stride 3 H W
-    pred[:, 0] = u.astype(np.float32) * INV[sim][:, None, None] + fields.smooth_field(N, H, W, seed + 4).astype(np.float32)
-    pred[:, 1] = v.astype(np.float32) * INV[sim][:, None, None] + fields.smooth_field(N, H, W, seed + 5).astype(np.float32)
-    pred[:, 2] = np.float32("nan")                                    # never read
     xc, yc = grid(H, W)
     host = dict(u=u.astype(np.float32), v=v.astype(np.float32), sim=sim, prev=prev, pred=pred)
     return dict(N=N, H=H, W=W, host=host, u=dev(u), v=dev(v), T=dev(T), sim=dev(sim, I32), prev=dev(prev, I32), paras=dev(paras),
@@ -110,18 +102,21 @@ def gather(c, idx, b, cursor, T=None, stride=None):
     return out.t.cpu(), want.t.cpu()
 
 
-@pytest.mark.parametrize("N,H,W", SIZES)
+@pytest.mark.parametrize("N,H,W", SIZES + [S.GATHER_SHAPE])
 def test_gather_equals_ts_build_input(N, H, W):
     c = case(N, H, W)
     idx = [(3 * j + 1) % N for j in range(N + 2)]            # permuted, with repeats
     for b, cursor in ((N + 2, 0), (3, 0), (3, N)):           # the whole list; its head; a tail of 2 items in 3 slots
         got, want = gather(c, idx, b, cursor)
         assert bool(torch.isfinite(want).all()) and torch.equal(got, want), (b, cursor)
+    if N == 1:                                               # (one snapshot: the grid-stride pass is what this size is here for)
+        assert (N, H, W) == S.GATHER_SHAPE and bool((got[:, 6] == c["T"][0].cpu()).all())
+        return
     got, _ = gather(c, [0, N - 1], 2, 0)                     # snapshots and simulations differ, so a mixed-up slot would show
     assert not torch.equal(got[0, 6], got[1, 6]) and not torch.equal(got[0, 3:6], got[1, 3:6]) and not torch.equal(got[0, 2], got[1, 2])
 
 
-@pytest.mark.parametrize("N,H,W", SIZES)
+@pytest.mark.parametrize("N,H,W", FINALIZE_SIZES)
 def test_table_and_profile_against_numpy(N, H, W):
     got = whole(N, H, W)
     table, profile, gate, pgate = reference(N, H, W)
@@ -130,6 +125,7 @@ def test_table_and_profile_against_numpy(N, H, W):
     for j in range(N):
         for q in range(10):
             print(f"item {j} {R.NAMES[q]}: got {t[j, q]!r} want {table[j, q]!r} |diff| {abs(t[j, q] - table[j, q]):.3e} gate {gate[j, q]:.3e}")
+    print(f"worst |got - want| / gate: table {S.worst_ratio(t, table, gate):.3e} profiles {S.worst_ratio(p, profile, pgate):.3e}")
     assert np.array_equal(t[:, R.MAX_COLS], table[:, R.MAX_COLS])                                 # maxima are exact
     assert R.close(t, table, gate) and R.close(p, profile, pgate)
     assert np.isfinite(t[:, [0, 1, 4, 5, 6, 7, 8, 9]]).all() and (t[:, [0, 1, 4, 5, 6, 7]] > 0).all()
@@ -151,7 +147,7 @@ def test_first_snapshots_have_no_baseline(N, H, W):
     assert same(none["table"][:, keep].contiguous(), whole(N, H, W)["table"][:, keep].contiguous()) and same(none["profile"], whole(N, H, W)["profile"])
 
 
-@pytest.mark.parametrize("N,H,W", SIZES)
+@pytest.mark.parametrize("N,H,W", FINALIZE_SIZES)
 def test_alone_equals_inside_a_batch(N, H, W):
     c, ref = case(N, H, W), whole(N, H, W)
     for s in range(N):
@@ -178,7 +174,7 @@ def test_list_walked_by_a_batch_that_does_not_divide_it():
     assert late["cursor"] == 5 and bool(torch.isnan(late["table"][:3]).all()) and same(late["table"][3:], ref["table"][3:])
 
 
-@pytest.mark.parametrize("N,H,W", SIZES)
+@pytest.mark.parametrize("N,H,W", FINALIZE_SIZES)
 def test_permuted_and_repeated_list(N, H, W):
     c, ref = case(N, H, W), whole(N, H, W)
     idx = [(3 * j + 1) % N for j in range(N + 2)]
@@ -186,6 +182,12 @@ def test_permuted_and_repeated_list(N, H, W):
     assert got["intact"] and got["cursor"] == N + 2
     sel = torch.tensor(idx)
     assert same(got["table"], ref["table"][sel]) and same(got["profile"], ref["profile"][sel])
+    if len(set(idx)) < N:                                    # (N a multiple of 3: that list names one snapshot)
+        idx = [(2 * j + 1) % N for j in range(N + 2)]
+        got = run(c, idx, 2)
+        sel = torch.tensor(idx)
+        assert len(set(idx)) == N and got["intact"] and got["cursor"] == N + 2
+        assert same(got["table"], ref["table"][sel]) and same(got["profile"], ref["profile"][sel])
 
 
 def test_simulations_use_their_own_scale():
@@ -205,11 +207,12 @@ def test_simulations_use_their_own_scale():
 
 
 def test_store_read_in_place_through_its_stride():
-    """T, u, v as channel 0 of [N,2,H,W] tensors (snapshot stride 2 H W, channel 1 NaN): the same bits as the dense store."""
-    N, H, W = SIZES[1]
-    c, ref = case(N, H, W), whole(N, H, W)
-    wide = lambda a: torch.stack([a, torch.full_like(a, float("nan"))], 1).contiguous()  # noqa: E731
-    got = run(c, list(range(N)), 3, uv=(wide(c["u"]), wide(c["v"])), stride=2 * H * W)
-    assert got["intact"] and same(got["table"], ref["table"]) and same(got["profile"], ref["profile"])
-    a, want = gather(c, [4, 0, 2], 3, 0, T=wide(c["T"]), stride=2 * H * W)
-    assert torch.equal(a, want)
+    """T, u, v as channel 0 of [N,2,H,W] tensors (snapshot stride 2 H W, channel 1 NaN): the same bits as the dense store.  At
+    5 x 7 x 70 and where the finalize takes three passes."""
+    for N, H, W in (SIZES[1], S.SERIES_SHAPES[2]):
+        c, ref = case(N, H, W), whole(N, H, W)
+        wide = lambda a: torch.stack([a, torch.full_like(a, float("nan"))], 1).contiguous()  # noqa: E731
+        got = run(c, list(range(N)), 3, uv=(wide(c["u"]), wide(c["v"])), stride=2 * H * W)
+        assert got["intact"] and same(got["table"], ref["table"]) and same(got["profile"], ref["profile"])
+        a, want = gather(c, [N - 1, 0, 2], 3, 0, T=wide(c["T"]), stride=2 * H * W)
+        assert torch.equal(a, want)
