@@ -1,5 +1,5 @@
 """Case tables, f64 references, derived bounds, comparison functions and mutants for the layout, fold, copy and bicubic kernels of
-csrc/elementwise.hip (tests/test_hip_glue_kernels.py on the GPU, tests/test_glue_cases_host.py on the CPU).  Nothing here touches a
+csrc/layout.hip, csrc/bicubic.hip and csrc/groupnorm.hip (tests/test_hip_glue_kernels.py on the GPU, tests/test_glue_cases_host.py on the CPU).  Nothing here touches a
 device: the GPU file hands what a kernel wrote to the `check_*` functions below, the host file hands them the mutants.
 
 Inputs are drawn with a seeded generator and rounded to the storage type first (f32, bf16, f16), so a reference sees what the

@@ -1,5 +1,5 @@
 """Case tables, input generators, f64 references and the derived tolerances of tests/test_hip_gn_act.py: the stand-alone
-GroupNorm / activation / pooling chain of csrc/elementwise.hip.  Nothing here touches a device.
+GroupNorm / activation / pooling chain of csrc/groupnorm.hip.  Nothing here touches a device.
 
 References are plain torch in f64 (F.group_norm with eps 1e-5, the exact activations, F.avg_pool2d in floor mode) applied to
 the values the kernels read: y after its rounding to the stored type, the gradient tensors in theirs.  Backward references

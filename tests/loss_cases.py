@@ -1,5 +1,5 @@
 """Case tables, f64 references, derived bounds, comparison functions and mutants for the Stokes loss kernels of csrc/loss.hip and
-the curl head of csrc/elementwise.hip (tests/test_hip_loss_kernels.py on the GPU, tests/test_loss_cases_host.py on the CPU).
+the curl head of csrc/curl_head.hip (tests/test_hip_loss_kernels.py on the GPU, tests/test_loss_cases_host.py on the CPU).
 
 The references restate oracle/ref_cpu.py with `ra` and `inv_h` as parameters (the oracle fixes both); the host tests assert once
 that the restatement equals the oracle at ra = 1, inv_h = 126.

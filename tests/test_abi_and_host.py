@@ -29,6 +29,19 @@ def test_library_exports_every_declared_symbol():
     assert _lib.load().mc_strerror(-2) == b"unsupported configuration"
 
 
+def test_build_lists_cover_csrc():
+    """Every csrc/*.hip is compiled, and every csrc/*.h is a dependency of the staleness check (a header missing from HEADERS
+    leaves stale objects in place after an edit)."""
+    from pbml_mantle_convection_amd import build_ext
+    files = os.listdir(build_ext.CSRC)
+    assert sorted(build_ext.SOURCES) == sorted(f for f in files if f.endswith(".hip"))
+    assert len(set(build_ext.SOURCES)) == len(build_ext.SOURCES)
+    assert {f for f in files if f.endswith(".h")} <= set(build_ext.HEADERS)
+    for h in build_ext.HEADERS:
+        assert os.path.isfile(os.path.join(build_ext.CSRC, h)), h
+    assert set(build_ext.EXTRA_FLAGS) <= set(build_ext.SOURCES)
+
+
 def test_struct_layouts_match_header():
     import ctypes as C
     from pbml_mantle_convection_amd import _lib

@@ -1,6 +1,6 @@
 """The kernels that carry every tensor between the convolutions, path by path against f64 and straight through the C ABI: the
 NCHW <-> CB8 converters and mc_sum_hw, mc_rect_copy, mc_gsrc_sum, the padding adjoint (mc_fold_padded, mc_fold_padded2,
-mc_fold_padded_dz) and the six bicubic entry points of csrc/elementwise.hip.  tests/glue_cases.py holds the case tables, the f64
+mc_fold_padded_dz) of csrc/layout.hip and csrc/groupnorm.hip and the six bicubic entry points of csrc/bicubic.hip.  tests/glue_cases.py holds the case tables, the f64
 references, the bounds derived from the kernels' rounding counts and the comparison functions; tests/test_glue_cases_host.py puts
 the mutants through the same comparisons and checks the launch arithmetic that makes each case reach its path.
 

@@ -1,4 +1,4 @@
-"""The stand-alone GroupNorm / activation / pooling kernels of csrc/elementwise.hip against f64, straight through the C ABI, at
+"""The stand-alone GroupNorm / activation / pooling kernels of csrc/groupnorm.hip against f64, straight through the C ABI, at
 the shapes where their index arithmetic, launch shapes and dispatch can go wrong (tests/gn_cases.py: the case tables, the f64
 references and the derived bounds).
 

@@ -1,4 +1,4 @@
-"""The Stokes loss kernels of csrc/loss.hip and the curl head of csrc/elementwise.hip against f64, term by term and straight through
+"""The Stokes loss kernels of csrc/loss.hip and the curl head of csrc/curl_head.hip against f64, term by term and straight through
 the C ABI, at the shapes that cross every kernel's tile seams (tests/loss_cases.py: the case tables, the f64 references, the
 derived bounds, the comparison functions; tests/test_loss_cases_host.py puts the mutants through the same comparisons).
 
