@@ -477,6 +477,8 @@ typedef struct {
   int32_t t_grad;          /* 1: T is a network output (gets a gradient); 0: T is given;   */
                            /* -1: the network has no temperature output (FluidNet family,  */
                            /* multigpu.py:138-195): T / gT may be NULL, uvp is (u, v[, p]) */
+                           /* -2: as -1, with the temperature term of the advection step   */
+                           /* (mc_advect_loss) as one more term of the average             */
 } mc_loss_desc;
 /* per-sample (min, max) over (H,W) of the truth channels u, v and (when ct >= 3) channel 2: mm [n][3][2] */
 int mc_loss_minmax(const float* uvp, int32_t n, int32_t ct, int32_t h, int32_t w, float* mm, void* stream);
@@ -516,6 +518,26 @@ int mc_momentum_adjoint(const mc_loss_desc* d, const float* T, int64_t pred_batc
 /* loss6 (+momentum) from the sums, exactly as get_loss combines them: out[8] f32 =
  * (loss, loss_true_u, loss_true_v, loss_p, loss_T, mean mass, mom, 0). */
 int mc_loss_finalize(const mc_loss_desc* d, const double* sums, float* out8, void* stream);
+/* Advection loss (build-defined, the reference's `-ad 1`; DESIGN.md 9 "Advection loss"): the temperature term of the FluidNet
+ * family.  Item b of x [n][x_channels >= 7][h][w] = (xc/4, yc/4, log10 eta/8, nd0, nd1, nd2, T) carries its own grid
+ * X = 4 x[0], Y = 4 x[1] (wall coordinates 0 / 4 and 0 / 1 substituted as mc_adnet_step does) and temperature T = x[6];
+ * uvp [n][uvp_channels][h][w] = truth (u, v[, p]), scaler [n] = s.
+ * mc_advect_loss_dt: dt[b] = fminf(0.5f cn_max dx_min_b / uv_b, 0.5f dx2 dx2 / (dx2 + dx2)), dx2 = dx_min_b^2, with dx_min_b
+ * the smallest interior X[i][j] - X[i][j-1] and uv_b = max(|s u_t|, |s v_t|) over the interior of item b -- mc_adnet_step's
+ * f32 expression, bit-identical to mc_rollout_dx_min + mc_rollout_dt on a shared grid; an item at rest gets the diffusive
+ * limit.  ws: MC_ADVECT_WS_PER_ITEM n uint32 scratch (per-workgroup partial maxima and minima; nothing to reset).
+ * mc_advect_loss (d->t_grad == -2; after mc_loss_fwd_bwd, before mc_loss_finalize): with A(u, v) = -u Dx(u) - v Dy(v), the
+ * upwind differences of T of ADNet.forward, e = dt[b] (A(s u_p, s v_p) - A(s u_t, s v_t)) on the interior;
+ * sums[MC_S_T_PLAIN] += sum |e| (1 + [j == 1] + [j == w-2])  (e^2 with d->l2) -- l1(ADNet(pred), ADNet(true)) at the given dt
+ * once mc_loss_finalize divides by n h w -- and d(loss)/d(u_p, v_p) is ADDED to the interior of gu, gv (batch stride
+ * pred_batch_stride, as u, v); their boundary rows and columns are not touched.  u_p == 0 contributes exactly 0.
+ * Both return MC_EINVAL, launching nothing, for a null pointer, n <= 0 or n > 65535, h < 5, w < 5 or x_channels < 7. */
+#define MC_ADVECT_WS_PER_ITEM 64
+int mc_advect_loss_dt(const float* uvp, int32_t uvp_channels, const float* x, int32_t x_channels, const float* scaler,
+                      int32_t n, int32_t h, int32_t w, float cn_max, uint32_t* ws, float* dt, void* stream);
+int mc_advect_loss(const mc_loss_desc* d, const float* u, const float* v, int64_t pred_batch_stride, const float* uvp,
+                   const float* x, int32_t x_channels, const float* scaler, const float* dt, double* sums, float* gu, float* gv,
+                   void* stream);
 
 /* ---- on-device batch assembly (ADTimeDataset.__getitem__, datasetio.py:229-280) -----------------
  * The whole dataset stays resident in HBM: T [m][h][w], uv [m][cy][h][w] (cy >= 2: u, v[, p]), t [m], paras [m][3] =

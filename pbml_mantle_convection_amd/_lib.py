@@ -16,6 +16,7 @@ ACTS = {"none": 0, "gelu": 1, "relu": 2, "silu": 3, "tanh": 4, "selu": 5, "elu":
 POST_NONE, POST_ACT, POST_GN_ACT = 0, 1, 2
 GSRC_NONE, GSRC_PLAIN, GSRC_PADFOLD, GSRC_PADFOLD_POOL, GSRC_PLAIN_POOL = 0, 1, 2, 3, 4
 LOSS_SLOTS = 16
+ADVECT_WS_PER_ITEM = 64                          # MC_ADVECT_WS_PER_ITEM: uint32 scratch words of mc_advect_loss_dt per item
 LOSS_TYPES = {"mae": 0, "mass": 1, "curl": 2}
 
 
@@ -221,6 +222,8 @@ SIGNATURES = {
     "mc_momentum_residual": (C.c_int, [_LD, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mc_momentum_adjoint": (C.c_int, [_LD, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mc_loss_finalize": (C.c_int, [_LD, _vp, _vp, _vp]),
+    "mc_advect_loss_dt": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _f32, _vp, _vp, _vp]),
+    "mc_advect_loss": (C.c_int, [_LD, _vp, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mc_spectral_slots": (_i32, [_i32, _i32]),
     "mc_spectral_analyze": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "mc_spectral_synthesize": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),

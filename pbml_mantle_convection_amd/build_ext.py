@@ -8,7 +8,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmantle_hip.so")
-SOURCES = ["layout.hip", "groupnorm.hip", "bicubic.hip", "curl_head.hip", "conv_api.hip", "conv_f32.hip", "conv_bf16.hip", "conv_rr_bf16.hip", "conv_learned.hip", "spectral.hip", "loss.hip", "rollout.hip", "ensemble_stats.hip", "rollout_score.hip", "series_score.hip", "optim.hip"]
+SOURCES = ["layout.hip", "groupnorm.hip", "bicubic.hip", "curl_head.hip", "conv_api.hip", "conv_f32.hip", "conv_bf16.hip", "conv_rr_bf16.hip", "conv_learned.hip", "spectral.hip", "loss.hip", "advect_loss.hip", "rollout.hip", "ensemble_stats.hip", "rollout_score.hip", "series_score.hip", "optim.hip"]
 HEADERS = ["common.h", "conv_common.h", "conv_rr.h", "launch.h", "philox.h", os.path.join("..", "..", "include", "mantle_hip.h")]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function",
          "-ffp-contract=off"]

@@ -77,7 +77,8 @@ __global__ __launch_bounds__(256) void k_loss(LossGeom g, const float* __restric
   const float* vt = uvp + ((size_t)n * g.ct + 1) * HW;
   const float* pt = g.d.p_pred ? uvp + ((size_t)n * g.ct + 2) * HW : nullptr;
   const float* Tt = hasT ? uvp + ((size_t)n * g.ct + (g.d.p_pred ? 3 : 2)) * HW : nullptr;
-  const float k = (g.d.p_pred ? 3.f : 2.f) + (hasT ? 1.f : 0.f);
+  // (t_grad == -2: no temperature output, but mc_advect_loss adds a temperature term to the average)
+  const float k = (g.d.p_pred ? 3.f : 2.f) + (hasT || g.d.t_grad == -2 ? 1.f : 0.f);
   const float NHW = (float)g.d.n * (float)HW;
   const float cdat = 1.0f / (k * NHW);
   float su = 1.f, sv = 1.f;
@@ -915,8 +916,10 @@ __global__ void k_loss_finalize(mc_loss_desc d, const double* __restrict__ s, fl
     lv += s[MC_S_DV] / (N * H * (W - 2));
     if (!d.loss_scale) { tu = lu; tv = lv; }   // reference aliasing quirk (multigpu.py:283-284)
   }
-  if (d.t_grad < 0) lT = 0.0;                                     // no temperature output: averaged over 3 / 2 terms (multigpu.py:173-177)
-  double loss = (lu + lv + lp + lT) / ((d.p_pred ? 3.0 : 2.0) + (d.t_grad < 0 ? 0.0 : 1.0));
+  // no temperature output: averaged over 3 / 2 terms (multigpu.py:173-177); t_grad == -2: the advection step's temperature
+  // term (mc_advect_loss) takes the place of the network's (:178-182)
+  if (d.t_grad == -1) lT = 0.0;
+  double loss = (lu + lv + lp + lT) / ((d.p_pred ? 3.0 : 2.0) + (d.t_grad == -1 ? 0.0 : 1.0));
   double mass = s[MC_S_MASS] / (N * (H - 2) * (W - 2));
   if (d.loss_type == 1) loss += mass;
   else if (d.loss_type == 2)

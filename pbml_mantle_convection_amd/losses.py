@@ -23,7 +23,8 @@ OUT_NAMES = ("loss", "loss_true_u", "loss_true_v", "loss_p", "loss_T", "mass", "
 class StokesLoss:
     def __init__(self, p_pred: bool, loss_type: str, loss_scale: bool = False, loss_derivative: bool = False,
                  norm: str = "l1", lambda_mom: float = 0.0, inv_h: float = 126.0, ra: float = 1.0,
-                 a_bound: float = 10.0, t_grad: bool = True, has_T: bool = True, curl_valid: bool = False):
+                 a_bound: float = 10.0, t_grad: bool = True, has_T: bool = True, curl_valid: bool = False,
+                 advect_cn: Optional[float] = None):
         if loss_type not in L.LOSS_TYPES:
             raise ValueError(f"loss_type must be one of {list(L.LOSS_TYPES)}")
         if norm not in ("l1", "l2"):
@@ -43,6 +44,14 @@ class StokesLoss:
         self.curl_valid = bool(curl_valid)
         if self.curl_valid and (loss_type != "curl" or self.has_T or self.p_pred):
             raise ValueError("curl_valid is FluidNet's head: loss_type 'curl', has_T = False, p_pred = False")
+        # advect_cn: the reference's `-ad 1` (DESIGN.md §9 "Advection loss"): a temperature term from ONE ADNet step of the
+        # predicted and of the true velocity on the item's own temperature, at the CFL step of the true velocity with
+        # CN_max = advect_cn (mc_advect_loss_dt -> mc_advect_loss after mc_loss_fwd_bwd)
+        self.advect_cn = None if advect_cn is None else float(advect_cn)
+        if self.advect_cn is not None and self.has_T:
+            raise ValueError("advect_cn is the FluidNet family's temperature term: it needs has_T = False (a Unet predicts T itself)")
+        if self.advect_cn is not None and not self.advect_cn > 0.0:
+            raise ValueError(f"advect_cn (the ADNet's CN_max) must be > 0, got {advect_cn}")
         self._shape = None
 
     # ------------------------------------------------------------------
@@ -75,6 +84,9 @@ class StokesLoss:
             self.sx = torch.empty((N, H, W), **f32)
             self.sy = torch.empty((N, H, W), **f32)
             self.eta = torch.empty((N, H, W), **f32)
+        if self.advect_cn is not None:
+            self.adv_dt = torch.zeros(N, **f32)
+            self.adv_ws = torch.zeros(L.ADVECT_WS_PER_ITEM * N, dtype=torch.int32, device=dev)
         self._shape = (N, Cc, H, W, str(dev))
 
     def channels_needed(self):
@@ -94,12 +106,14 @@ class StokesLoss:
         return FUSED_LOSS and self.has_T and self.loss_type != "curl"
 
     def evaluate(self, y: Optional[torch.Tensor], uvp: torch.Tensor, yc: Optional[torch.Tensor] = None,
-                 paras: Optional[torch.Tensor] = None, scaler: Optional[torch.Tensor] = None, cb8=None):
+                 paras: Optional[torch.Tensor] = None, scaler: Optional[torch.Tensor] = None, cb8=None, advect=None):
         """y: network output [N, C, H, W] f32 (Unet.features / ConvAE output; [N, C, H + 2, W + 2] with curl_valid);
         uvp: truth [N, 2|3|4, H, W] f32.  Returns (out8, gy): out8 = (loss, true_u, true_v, loss_p, loss_T, mass,
         momentum, 0) on device; gy = d(loss)/d(y).
         cb8 (only with `fusable()`): (buf, mean, crop, (N, C, H, W)) -- the last convolution's f32 output in the CB8 layout
-        [N][ceil(C / 8)][H][W + 2 crop][8] and its per-(sample, channel) spatial means; y is not read then (may be None)."""
+        [N][ceil(C / 8)][H][W + 2 crop][8] and its per-(sample, channel) spatial means; y is not read then (may be None).
+        advect (with `advect_cn`, and only then): (x, scaler) -- the batch's input x [N, >= 7, H, W] f32 = (xc/4, yc/4,
+        log10 eta/8, nd0, nd1, nd2, T, ...) and the velocity scale [N]; out8[4] is then the advection step's temperature error."""
         L.require_cuda(uvp, "uvp")
         if cb8 is not None:
             if not self.fusable():
@@ -121,12 +135,26 @@ class StokesLoss:
         ct = (3 if self.p_pred else 2) + (1 if self.has_T else 0)
         if tuple(uvp.shape) != (N, ct, H, W):
             raise ValueError(f"uvp must be [{N},{ct},{H},{W}], got {tuple(uvp.shape)}")
+        if (advect is not None) != (self.advect_cn is not None):
+            raise ValueError("advect=(x, scaler) goes with a loss built with advect_cn, and a loss built with advect_cn needs it")
+        if advect is not None:
+            ax, asc = advect
+            L.require_cuda(ax, "advect x")
+            L.require_cuda(asc, "advect scaler")
+            if ax.dim() != 4 or ax.shape[0] != N or ax.shape[1] < 7 or tuple(ax.shape[2:]) != (H, W):
+                raise ValueError(f"advect x must be [{N}, >= 7, {H}, {W}], got {tuple(ax.shape)}")
+            if asc.numel() != N:
+                raise ValueError(f"advect scaler must hold {N} values, got {tuple(asc.shape)}")
+            if ax.dtype != torch.float32 or not ax.is_contiguous():
+                ax = ax.float().contiguous()
+            if asc.dtype != torch.float32 or not asc.is_contiguous():
+                asc = asc.float().contiguous()
         self._alloc(N, Cc, H, W, dev)
         st = L.stream()
         HW = H * W
         d = L.LossDesc(N, H, W, int(self.p_pred), L.LOSS_TYPES[self.loss_type], int(self.loss_scale),
                        int(self.loss_derivative), int(self.norm == "l2"), self.lambda_mom, self.inv_h, self.ra,
-                       int(self.t_grad) if self.has_T else -1)
+                       int(self.t_grad) if self.has_T else (-1 if advect is None else -2))
         self.sums.zero_()
         if self.loss_scale:
             L.call("mc_loss_minmax", L.ptr(uvp), N, ct, H, W, L.ptr(self.mm), st)
@@ -201,6 +229,11 @@ class StokesLoss:
         ppbs = Cc * HW
         L.call("mc_loss_fwd_bwd", C.byref(d), u, v, p, T, pbs, ppbs, L.ptr(uvp), L.ptr(self.mm), L.ptr(self.sums), gu,
                gv, gp, gT, st)
+        if advect is not None:
+            L.call("mc_advect_loss_dt", L.ptr(uvp), ct, L.ptr(ax), int(ax.shape[1]), L.ptr(asc), N, H, W, self.advect_cn,
+                   L.ptr(self.adv_ws), L.ptr(self.adv_dt), st)
+            L.call("mc_advect_loss", C.byref(d), u, v, pbs, L.ptr(uvp), L.ptr(ax), int(ax.shape[1]), L.ptr(asc),
+                   L.ptr(self.adv_dt), L.ptr(self.sums), gu, gv, st)
         if self.lambda_mom != 0.0:
             if yc is None or paras is None or scaler is None:
                 raise ValueError("the momentum term needs yc [H,W], paras [N,3] and scaler [N]")
@@ -224,18 +257,18 @@ class StokesLoss:
         L.call("mc_loss_finalize", C.byref(d), L.ptr(self.sums), L.ptr(self.out8), st)
         return self.out8, self.gy
 
-    def __call__(self, y, uvp, yc=None, paras=None, scaler=None):
+    def __call__(self, y, uvp, yc=None, paras=None, scaler=None, advect=None):
         """Autograd-visible: returns out8 whose element 0 back-propagates d(loss)/dy into y."""
-        return _LossFn.apply(self, y, uvp, yc, paras, scaler)
+        return _LossFn.apply(self, y, uvp, yc, paras, scaler, advect)
 
 
 class _LossFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, loss_obj, y, uvp, yc, paras, scaler):
-        out8, gy = loss_obj.evaluate(y.contiguous(), uvp, yc, paras, scaler)
+    def forward(ctx, loss_obj, y, uvp, yc, paras, scaler, advect=None):
+        out8, gy = loss_obj.evaluate(y.contiguous(), uvp, yc, paras, scaler, advect=advect)
         ctx.gy = gy.clone()
         return out8.clone()
 
     @staticmethod
     def backward(ctx, gout):
-        return None, ctx.gy * gout[0], None, None, None, None
+        return None, ctx.gy * gout[0], None, None, None, None, None

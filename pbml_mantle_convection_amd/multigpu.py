@@ -30,7 +30,7 @@ from . import _lib as L
 from .datasetio import *  # noqa: F401,F403  (reference does the same star import)
 from .hipnet import FlatParams
 from .losses import StokesLoss
-from .pytorch_networks_convae import ConvAE, FluidNet, NewFluidNet, Unet, count_parameters
+from .pytorch_networks_convae import ADNet, ConvAE, FluidNet, NewFluidNet, Unet, count_parameters
 
 
 def ddp_setup(rank, world_size, master_port, backend: Optional[str] = None):
@@ -175,8 +175,19 @@ class Trainer:
         fluid = "fluidnet" in network          # the reference's `"fluidnet" in self.net` branch of get_loss (:138)
         if fluid and lambda_mom != 0.0:
             raise NotImplementedError("the momentum residual needs the temperature output of the Unet")
+        # model_AD (the reference's `-ad 1`, "add advection to loss", :156-182): for the FluidNet family the loss gains a
+        # temperature term from one ADNet step of the predicted and of the true velocity (DESIGN.md §9 "Advection loss");
+        # only the net's CN_max is read, the step itself is part of the loss kernels.  The reference's other branches never
+        # read model_AD (:196-305)
+        self.advect_cn = None
         if model_AD is not None:
-            raise NotImplementedError("model_AD (advection net) is out of scope of the training hot path")
+            if not isinstance(model_AD, ADNet):
+                raise TypeError(f"model_AD must be a pytorch_networks_convae.ADNet (or None), got {type(model_AD).__name__}")
+            if fluid:
+                self.advect_cn = float(model_AD.CN_max)
+            else:
+                print(f"[mantle] network={network!r} does not use model_AD (as in the reference): the advection net is ignored",
+                      file=sys.stderr, flush=True)
         self.gpu_id = gpu_id
         self.device = torch.device("cuda", gpu_id) if isinstance(gpu_id, int) else torch.device(gpu_id)
         self.train_data, self.cv_data = train_data, cv_data
@@ -194,7 +205,7 @@ class Trainer:
                       "gradients); MANTLE_MIXED=0 keeps plain bf16", file=sys.stderr, flush=True)
         if precision is not None:
             self.model_uvp.set_precision(precision)
-        self.model_AD = None
+        self.model_AD = model_AD
         self.p_pred, self.nn_dir, self.debug, self.net = p_pred, nn_dir, debug, network
         self.loss_scale, self.loss_derivative, self.roll_forward = loss_scale, loss_derivative, roll_forward
         self.start_epoch, self.loss_type = epoch, loss_type
@@ -230,7 +241,8 @@ class Trainer:
         self.loss = StokesLoss(p_pred if network != "convae" else False,
                                loss_type if network != "convae" else "mae", loss_scale, loss_derivative, norm=norm,
                                lambda_mom=lambda_mom, a_bound=a_bound, has_T=not fluid,
-                               curl_valid=isinstance(self.model_uvp, FluidNet))   # (u, v on H x W from an (H+2) x (W+2) output)
+                               curl_valid=isinstance(self.model_uvp, FluidNet),   # (u, v on H x W from an (H+2) x (W+2) output)
+                               advect_cn=self.advect_cn)
         if network == "convae" or fluid:
             self.chan_scale = None                    # these nets see gVTp as it is (reference :139)
         else:
@@ -322,10 +334,10 @@ class Trainer:
                 gVTp = self._roll_chain(gVTp.contiguous(), None if paras is None else paras.to(self.device), self._features)
         y = self._features(gVTp)
         sc = None
-        if self.loss.lambda_mom != 0.0:
+        if self.loss.lambda_mom != 0.0 or self.advect_cn is not None:
             sc = scaler.to(self.device, torch.float32) if scaler is not None else None
         out8 = self.loss(y, uvp, yc.to(self.device) if yc is not None else None,
-                         paras.to(self.device) if paras is not None else None, sc)
+                         paras.to(self.device) if paras is not None else None, sc, self._advect_args(gVTp, sc))
         return out8[0], out8[1].detach(), out8[2].detach(), out8[3].detach(), out8[4].detach(), out8[5].detach()
 
     # ------------------------------------------------------------------ fused step
@@ -364,11 +376,19 @@ class Trainer:
         if y is None:
             out8, gy = loss.evaluate(None, uvp, yc, paras, scaler, cb8=eng.output_cb8())
         else:
-            out8, gy = loss.evaluate(y, uvp, yc, paras, scaler)
+            out8, gy = loss.evaluate(y, uvp, yc, paras, scaler, advect=self._advect_args(gVTp, scaler))
         if train:
             self.flat.grad.zero_()
             eng.backward(gy, params, self.flat.views(self.flat.grad), gsum=loss.gradient_sums() if GSUM_FROM_LOSS else None)
         return out8
+
+    def _advect_args(self, gVTp, scaler):
+        """(x, scaler) of the advection loss, None without model_AD: the batch's own input carries the grid and the temperature."""
+        if self.advect_cn is None:
+            return None
+        if scaler is None:
+            raise ValueError("the advection loss (model_AD) needs the batch's velocity scaler [N]")
+        return gVTp, scaler
 
     def _check_single_mesh(self, yc):
         """The momentum residual evaluates the viscosity with ONE depth grid yc [H, W] for the whole batch (sample 0's).
@@ -523,7 +543,7 @@ class Trainer:
         need = self.loss.lambda_mom != 0.0
         yc = yc.to(self.device, torch.float32) if (need and yc is not None) else None
         paras = paras.to(self.device, torch.float32) if ((need or self._rolls()) and paras is not None) else None
-        scaler = scaler.to(self.device, torch.float32) if (need and scaler is not None) else None
+        scaler = scaler.to(self.device, torch.float32) if ((need or self.advect_cn is not None) and scaler is not None) else None
         return gVTp, uvp, yc, paras, scaler
 
     def _run_batch(self, gVTp, uvp, scaler, is_train, paras=None, yc=None, sync=True):
@@ -679,7 +699,8 @@ class Trainer:
                                 "strings, lists and dicts only (it is read with weights_only=True)")
         return dict(                                                   # (the .cpu() copies are the device sync)
             header=dict(version=STATE_VERSION, epoch=int(self.epoch_done), world=int(self.world),
-                        precision=str(self.model_uvp.precision), network=str(self.net), numel=int(self.flat.numel)),
+                        precision=str(self.model_uvp.precision), network=str(self.net), numel=int(self.flat.numel),
+                        advect=self.advect_cn is not None, CN_max=0.0 if self.advect_cn is None else float(self.advect_cn)),
             layout=self._layout(),
             optimizer=dict(param=self.flat.param.detach().cpu(), exp_avg=self.exp_avg.cpu(), exp_avg_sq=self.exp_avg_sq.cpu(),
                            step_count=self.step_count.cpu(), lr=float(g["lr"]), betas=[b1, b2], eps=eps, weight_decay=wd,
@@ -695,6 +716,11 @@ class Trainer:
         for k, v in mine.items():
             if h[k] != v:
                 raise ValueError(f"run state was written with {k}={h[k]!r}, this run has {k}={v!r}: it cannot continue exactly")
+        # the advection loss is part of what the step computes (a state written before the term existed has neither key: off)
+        had = (bool(h.get("advect", False)), float(h.get("CN_max", 0.0)))
+        now = (self.advect_cn is not None, 0.0 if self.advect_cn is None else float(self.advect_cn))
+        if had != now:
+            raise ValueError(f"run state was written with (advect, CN_max) = {had}, this run has {now}: it cannot continue exactly")
         a, b = state["layout"], self._layout()
         for i, (n0, s0, o0) in enumerate(zip(a["names"], a["shapes"], a["offsets"])):
             if i >= len(b["names"]):
@@ -851,11 +877,11 @@ def load_train_objs(rank, world_size, nn_dir, data_dir, levels, c_i, c_h, c_o, a
                     repeats, kernel, milestones, sims_vec, times_vec, sims_vec_init, times_vec_init, use_skip=False,
                     p_pred=False, spectral_conv=False, dilation=1, a_bound=10, restart=False, advect=False,
                     network="fluidnet", scale=True, noise=0.0, debug=False, blurr=False, l2_reg=0.0, dropout=0.0,
-                    roll_forward=1, factor=2, multi_scales=[], synthetic=None):
+                    roll_forward=1, factor=2, multi_scales=[], synthetic=None, ad_cn=2e4):
     """Same signature and return tuple as the reference (:453-769).  `synthetic=dict(n=..., H=..., W=...)`
-    substitutes the seeded synthetic dataset for the absent /plp_scr1 data files."""
-    if advect:
-        raise NotImplementedError("advect=True (ADNet) is out of scope")
+    substitutes the seeded synthetic dataset for the absent /plp_scr1 data files.  advect=True returns the reference's
+    `ADNet(device=rank, CN_max=2e4)` (:615-617) as model_AD (`ad_cn`: another CN_max)."""
+    model_AD = ADNet(device=rank, CN_max=ad_cn) if advect else None
     model_uvp = build_model(network, levels, c_i, c_h, c_o, rank, act_fn, r_p, loss_type, use_symm, repeats, kernel,
                             use_skip, p_pred, spectral_conv, dilation, a_bound, blurr, dropout, factor=factor)
     print(count_parameters(model_uvp))
@@ -900,7 +926,7 @@ def load_train_objs(rank, world_size, nn_dir, data_dir, levels, c_i, c_h, c_o, a
                                                 times_vec=times_vec_init[an][lo_i:hi_i], **kw)
     optimizer = torch.optim.Adam([{"params": model_uvp.parameters(), "lr": start_lr, "weight_decay": l2_reg}])
     scheduler = torch.optim.lr_scheduler.MultiStepLR(optimizer, milestones=milestones, gamma=0.5)
-    return dataset, dataset_init, model_uvp, None, optimizer, scheduler, epoch
+    return dataset, dataset_init, model_uvp, model_AD, optimizer, scheduler, epoch
 
 
 def prepare_dataloader(dataset: Dataset, batch_size: int, world_size, rank):
@@ -931,7 +957,7 @@ def main(rank: int, world_size: int, save_every: int, total_epochs: int, batch_s
          restart=False, advect=False, network="fluidnet", debug=False, scale=True, blurr=False, master_port=366,
          l2_reg=0.0, dropout=0.0, loss_scale=False, loss_derivative=False, roll_forward=1, factor=2, multi_scales=[],
          synthetic=None, precision=None, lambda_mom=0.0, use_graph=False, clip_norm=0.0, skip_nonfinite=False, noise=0.0,
-         resident=False, save_state=False):
+         resident=False, save_state=False, ad_cn=2e4):
     if resident and synthetic is not None:
         raise ValueError("--resident 1 keeps shard-file datasets in HBM; the --synthetic set has no shard files (leave "
                          "--resident at 0 with --synthetic)")
@@ -941,7 +967,7 @@ def main(rank: int, world_size: int, save_every: int, total_epochs: int, batch_s
         milestones, sims_vec, times_vec, sims_vec_init, times_vec_init, use_skip=use_skip, p_pred=p_pred,
         spectral_conv=spectral_conv, dilation=dilation, a_bound=a_bound, restart=restart, advect=advect,
         network=network, scale=scale, noise=noise, debug=debug, blurr=blurr, l2_reg=l2_reg, dropout=dropout,
-        roll_forward=roll_forward, factor=factor, multi_scales=multi_scales, synthetic=synthetic)
+        roll_forward=roll_forward, factor=factor, multi_scales=multi_scales, synthetic=synthetic, ad_cn=ad_cn)
     if resident:
         train_data, cv_data = (resident_loader(dataset[an], dataset_init[an], batch_size, rank, world_size,
                                                len(sims_vec[an]), seed=torch.initial_seed()) for an in ("train", "cv"))
@@ -1013,6 +1039,7 @@ def build_arg_parser():
     p.add_argument("--skip_nonfinite", type=int, default=0)       # 1: skip the optimizer step of a non-finite gradient
     p.add_argument("--resident", type=int, default=0)             # 1: datasets resident in HBM, batches assembled inside the step
     p.add_argument("--save_state", type=int, default=0)           # 1: write the whole training state beside the weights; -rst 1 then resumes bit for bit
+    p.add_argument("--ad_cn", type=float, default=2e4)            # CN_max of the advection net of -ad 1 (the reference's literal)
     return p
 
 
@@ -1091,7 +1118,7 @@ def cli(argv=None):
             a.use_skip == 1, p_pred, a.spectral_conv == 1, a.dilation, a.a_bound, a.restart == 1, a.advect == 1,
             a.network, debug, a.scale == 1, a.blurr == 1, a.master_port, a.l2_reg, a.drop_rate, a.loss_scale == 1,
             a.loss_derivative == 1, a.roll_forward, a.factor, a.multi_scales, synthetic, a.precision, a.lambda_mom,
-            a.use_graph == 1, a.clip_norm, a.skip_nonfinite == 1, a.noise, a.resident == 1, a.save_state == 1)
+            a.use_graph == 1, a.clip_norm, a.skip_nonfinite == 1, a.noise, a.resident == 1, a.save_state == 1, a.ad_cn)
     if world_size == 1:
         main(0, *args)
     else:
