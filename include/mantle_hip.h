@@ -458,6 +458,26 @@ int mc_curl_valid_fwd(const float* a, int32_t n, int32_t h, int32_t w, int64_t i
 int mc_curl_valid_bwd(const float* gu, const float* gv, int32_t n, int32_t h, int32_t w, float a_bound, float* ga,
                       int64_t g_batch_stride, void* stream);
 
+/* ---- blurred streamfunction (`-blurr 1`; NewFluidNet :1357-1361, FluidNet :1682-1686): the four heads above with
+ *      A = a_bound * a replaced by its 3 x 3 box mean over the replicate-padded plane the head reads (hp x wp = h x w for the
+ *      wall form, (h+2) x (w+2) for the valid form):
+ *        B[i][j] = wb * sum_{di, dj in {-1,0,1}} A[clamp(i+di, 0, hp-1)][clamp(j+dj, 0, wp-1)],  wb = 1.0f / 9.0f (the f32 value);
+ *      u, v are what the unblurred twin makes of B (wall form: corners exactly 0; t_out = clip(t_in) as before, T is not
+ *      blurred).  The adjoints are the transposes: the clamped mean is symmetric, so ga is the same clamped 3 x 3 sum of the
+ *      twin's stencil adjoint.  The mean is fused: forward is one launch (plus the clip when t_in is given), backward the
+ *      twin's launches (fold + gather / one gather), B and its gradient never reach memory, every output pixel is written
+ *      once, no atomics (bit-reproducible).  Arguments, batch strides, workspace size and MC_EINVAL cases are the twins';
+ *      all four also return MC_EINVAL for n > 65535 (the batch is a grid dimension). --- */
+int mc_curl_blur_head_fwd(const float* a, const float* t_in, int32_t n, int32_t h, int32_t w, int64_t in_batch_stride,
+                          float a_bound, float t_lo, float t_hi, float* u, float* v, float* t_out, void* stream);
+int mc_curl_blur_head_bwd(const float* gu, const float* gv, const float* gt_out, const float* t_in, int32_t n, int32_t h,
+                          int32_t w, float a_bound, float t_lo, float t_hi, float* ga, float* gt_in,
+                          int64_t g_batch_stride, int64_t in_batch_stride, float* ws, void* stream);
+int mc_curl_blur_valid_fwd(const float* a, int32_t n, int32_t h, int32_t w, int64_t in_batch_stride, float a_bound, float* u,
+                           float* v, void* stream);
+int mc_curl_blur_valid_bwd(const float* gu, const float* gv, int32_t n, int32_t h, int32_t w, float a_bound, float* ga,
+                           int64_t g_batch_stride, void* stream);
+
 /* ---- loss (Trainer.loss_fn multigpu.py:122-134; get_loss :250-305) + build-defined momentum -- */
 #define MC_LOSS_SLOTS 16
 enum { MC_S_U_SCALED = 0, MC_S_U_PLAIN, MC_S_V_SCALED, MC_S_V_PLAIN, MC_S_P_PLAIN, MC_S_T_PLAIN,

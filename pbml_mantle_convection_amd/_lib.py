@@ -186,6 +186,12 @@ SIGNATURES = {
                                    _vp, _vp]),
     "mc_curl_valid_fwd": (C.c_int, [_vp, _i32, _i32, _i32, _i64, _f32, _vp, _vp, _vp]),
     "mc_curl_valid_bwd": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _f32, _vp, _i64, _vp]),
+    # (`-blurr 1`: the four heads with the 3 x 3 box mean of the streamfunction inside; the twins' arguments)
+    "mc_curl_blur_head_fwd": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i64, _f32, _f32, _f32, _vp, _vp, _vp, _vp]),
+    "mc_curl_blur_head_bwd": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _f32, _f32, _vp, _vp, _i64, _i64,
+                                        _vp, _vp]),
+    "mc_curl_blur_valid_fwd": (C.c_int, [_vp, _i32, _i32, _i32, _i64, _f32, _vp, _vp, _vp]),
+    "mc_curl_blur_valid_bwd": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _f32, _vp, _i64, _vp]),
     "mc_assemble_adtime_batch": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp,
                                            _vp, _vp, _vp]),
     "mc_assemble_newad_batch": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),

@@ -137,6 +137,108 @@ __global__ void __launch_bounds__(256) k_curl_valid_bwd(const float* __restrict_
   ga_[(size_t)n * gabs + (size_t)r * (W + 2) + c] = ab * 0.5f * acc;
 }
 
+// =================================================================================================
+// blurred streamfunction (NewFluidNet :1357-1361, FluidNet :1682-1686): B = 3 x 3 box mean of A = a_bound * a over the
+// replicate-padded Hp x Wp plane, weight w = float(1) / float(9) on every tap; u, v are the heads above applied to B.  The
+// mean is fused into the head, so neither B nor its gradient ever exists in memory.
+// =================================================================================================
+constexpr int BT_X = 64, BT_Y = 16;                 // output tile of one 64 x 4 block: every thread makes four rows
+constexpr float BLUR_W = 1.0f / 9.0f;               // the f32 weight of the reference's filter
+
+// Forward, both forms.  A centre (ye, xe) of the plane gives
+//   u_in = 0.5 (B[ye+1][xe] - B[ye-1][xe]),  v_in = -0.5 (B[ye][xe+1] - B[ye][xe-1]);
+// the middle row (column) of the two box sums is shared and cancels, so twelve taps remain per component.
+// WALL (Unet / NewFluidNet form, output Hp x Wp): ye = clamp(y, 1, Hp-2), xe = clamp(x, 1, Wp-2) is the replicate pad of
+// u_in / v_in, wall columns of u and wall rows of v change sign, corners are 0.  Otherwise (FluidNet form, output
+// (Hp-2) x (Wp-2)): ye = y + 1, xe = x + 1.  The block stages the (BT_Y + 4) x (BT_X + 4) window around its centres with
+// indices clamped to the plane: the clamp is the blur's replicate rule, and no read leaves the plane of item n.
+template <bool WALL>
+__global__ void __launch_bounds__(256) k_curl_blur_fwd(const float* __restrict__ a_, int Hp, int Wp, int64_t abs_, float ab,
+                                                       float* __restrict__ u, float* __restrict__ v) {
+  __shared__ float s[BT_Y + 4][BT_X + 4];
+  const int n = blockIdx.z, tx0 = blockIdx.x * BT_X, ty0 = blockIdx.y * BT_Y;
+  const int Ho = WALL ? Hp : Hp - 2, Wo = WALL ? Wp : Wp - 2;
+  const int oy = (WALL ? min(max(ty0, 1), Hp - 2) : ty0 + 1) - 2, ox = (WALL ? min(max(tx0, 1), Wp - 2) : tx0 + 1) - 2;
+  const float* a = a_ + (size_t)n * abs_;
+  for (int r = threadIdx.y; r < BT_Y + 4; r += 4) {
+    const float* row = a + (size_t)min(max(oy + r, 0), Hp - 1) * Wp;
+    for (int c = threadIdx.x; c < BT_X + 4; c += 64) s[r][c] = row[min(max(ox + c, 0), Wp - 1)];
+  }
+  __syncthreads();
+  const int x = tx0 + threadIdx.x;
+  if (x >= Wo) return;
+  const float k = ab * (0.5f * BLUR_W);
+  const int lx = (WALL ? min(max(x, 1), Wp - 2) : x + 1) - ox;
+  const bool wall_x = WALL && (x == 0 || x == Wp - 1);
+#pragma unroll
+  for (int j = 0; j < BT_Y / 4; ++j) {
+    const int y = ty0 + threadIdx.y + 4 * j;
+    if (y >= Ho) break;
+    const int ly = (WALL ? min(max(y, 1), Hp - 2) : y + 1) - oy;
+    const bool wall_y = WALL && (y == 0 || y == Hp - 1);
+    float su[3], sv[3];
+#pragma unroll
+    for (int d = -1; d <= 1; ++d) {
+      su[d + 1] = (s[ly + 2][lx + d] - s[ly - 2][lx + d]) + (s[ly + 1][lx + d] - s[ly - 1][lx + d]);
+      sv[d + 1] = (s[ly + d][lx + 2] - s[ly + d][lx - 2]) + (s[ly + d][lx + 1] - s[ly + d][lx - 1]);
+    }
+    const float uu = k * ((su[0] + su[1]) + su[2]), vv = -(k * ((sv[0] + sv[1]) + sv[2]));
+    const bool corner = wall_x && wall_y;
+    const size_t o = ((size_t)n * Ho + y) * Wo + x;
+    u[o] = corner ? 0.f : (wall_x ? -uu : uu);
+    v[o] = corner ? 0.f : (wall_y ? -vv : vv);
+  }
+}
+
+// Adjoint, both forms: eu, ev [n][Hp-2][Wp-2] are the gradients w.r.t. u_in, v_in (k_curl_bwd_fold's output, or gu, gv
+// themselves in the FluidNet form).  The stencil adjoint
+//   gB[r][c] = ((eu[r-2][c-1] - eu[r][c-1]) - ev[r-1][c-2]) + ev[r-1][c]     (terms outside eu / ev are 0)
+// is formed while the block stages its (BT_Y + 2) x (BT_X + 2) window, again at indices clamped to the plane.  The clamped
+// box mean is a symmetric matrix (rows 0 and Hp-1 count themselves twice), so its transpose is the same clamped 3 x 3 sum:
+//   ga[r][c] = a_bound 0.5 w sum_{dr, dc} gB[clamp(r+dr)][clamp(c+dc)].
+// Every pixel of the plane is written once by one thread in a fixed order: no memset, no atomics.
+__device__ __forceinline__ float curl_gB(const float* __restrict__ eu, const float* __restrict__ ev, int r, int c, int Hi, int Wi) {
+  float acc = 0.f;
+  const int j = c - 1, i = r - 1;
+  if (j >= 0 && j < Wi) {
+    if (r - 2 >= 0 && r - 2 < Hi) acc += eu[(size_t)(r - 2) * Wi + j];
+    if (r < Hi) acc -= eu[(size_t)r * Wi + j];
+  }
+  if (i >= 0 && i < Hi) {
+    if (c - 2 >= 0 && c - 2 < Wi) acc -= ev[(size_t)i * Wi + c - 2];
+    if (c < Wi) acc += ev[(size_t)i * Wi + c];
+  }
+  return acc;
+}
+
+__global__ void __launch_bounds__(256) k_curl_blur_bwd(const float* __restrict__ eu_, const float* __restrict__ ev_, int Hp, int Wp,
+                                                       float ab, float* __restrict__ ga_, int64_t gabs) {
+  __shared__ float s[BT_Y + 2][BT_X + 2];
+  const int n = blockIdx.z, tx0 = blockIdx.x * BT_X, ty0 = blockIdx.y * BT_Y;
+  const int Hi = Hp - 2, Wi = Wp - 2;
+  const float* eu = eu_ + (size_t)n * Hi * Wi;
+  const float* ev = ev_ + (size_t)n * Hi * Wi;
+  for (int r = threadIdx.y; r < BT_Y + 2; r += 4) {
+    const int pr = min(max(ty0 - 1 + r, 0), Hp - 1);
+    for (int c = threadIdx.x; c < BT_X + 2; c += 64) s[r][c] = curl_gB(eu, ev, pr, min(max(tx0 - 1 + c, 0), Wp - 1), Hi, Wi);
+  }
+  __syncthreads();
+  const int c = tx0 + threadIdx.x;
+  if (c >= Wp) return;
+  const float k = ab * (0.5f * BLUR_W);
+  const int lx = threadIdx.x + 1;
+  float* ga = ga_ + (size_t)n * gabs;
+#pragma unroll
+  for (int j = 0; j < BT_Y / 4; ++j) {
+    const int ly = threadIdx.y + 4 * j + 1, r = ty0 + ly - 1;
+    if (r >= Hp) break;
+    float t[3];
+#pragma unroll
+    for (int d = -1; d <= 1; ++d) t[d + 1] = (s[ly + d][lx - 1] + s[ly + d][lx]) + s[ly + d][lx + 1];
+    ga[(size_t)r * Wp + c] = k * ((t[0] + t[1]) + t[2]);
+  }
+}
+
 __global__ void k_clip_fwd(const float* __restrict__ t, int hw, int64_t bs, float lo, float hi, float* __restrict__ o) {
   const int n = blockIdx.y;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < hw; i += gridDim.x * blockDim.x)
@@ -197,6 +299,58 @@ int mc_curl_valid_bwd(const float* gu, const float* gv, int32_t n, int32_t h, in
   if (!gu || !gv || !ga || n <= 0 || n > 65535 || h <= 0 || w <= 0 || g_batch_stride < (int64_t)(h + 2) * (w + 2)) return MC_EINVAL;
   dim3 g(cdiv(w + 2, 64), cdiv(h + 2, 4), n);
   hipLaunchKernelGGL(k_curl_valid_bwd, g, dim3(64, 4), 0, (hipStream_t)stream, gu, gv, h, w, a_bound, ga, g_batch_stride);
+  MC_CHECK_LAUNCH();
+  return MC_OK;
+}
+
+// ---- the same four heads with the 3 x 3 box mean of the streamfunction inside (same arguments, same workspace) ----
+int mc_curl_blur_head_fwd(const float* a, const float* t_in, int32_t n, int32_t h, int32_t w, int64_t in_batch_stride,
+                          float a_bound, float t_lo, float t_hi, float* u, float* v, float* t_out, void* stream) {
+  if (!a || !u || !v || n <= 0 || n > 65535 || h < 3 || w < 3 || ((t_in == nullptr) != (t_out == nullptr))) return MC_EINVAL;
+  dim3 g(cdiv(w, BT_X), cdiv(h, BT_Y), n);
+  hipLaunchKernelGGL(k_curl_blur_fwd<true>, g, dim3(64, 4), 0, (hipStream_t)stream, a, h, w, in_batch_stride, a_bound, u, v);
+  if (t_in) {
+    dim3 gc(min(cdiv(h * w, 256), 4096), n);
+    hipLaunchKernelGGL(k_clip_fwd, gc, dim3(256), 0, (hipStream_t)stream, t_in, h * w, in_batch_stride, t_lo, t_hi, t_out);
+  }
+  MC_CHECK_LAUNCH();
+  return MC_OK;
+}
+
+int mc_curl_blur_head_bwd(const float* gu, const float* gv, const float* gt_out, const float* t_in, int32_t n, int32_t h,
+                          int32_t w, float a_bound, float t_lo, float t_hi, float* ga, float* gt_in, int64_t g_batch_stride,
+                          int64_t in_batch_stride, float* ws, void* stream) {
+  if (!gu || !gv || !ga || !ws || n <= 0 || n > 65535 || h < 3 || w < 3) return MC_EINVAL;
+  if (gt_in && (!gt_out || !t_in)) return MC_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  float* eu = ws;
+  float* ev = ws + (size_t)n * (h - 2) * (w - 2);
+  dim3 g1(min(cdiv((h - 2) * (w - 2), 256), 4096), n);
+  hipLaunchKernelGGL(k_curl_bwd_fold, g1, dim3(256), 0, s, gu, gv, h, w, eu, ev);
+  dim3 g2(cdiv(w, BT_X), cdiv(h, BT_Y), n);
+  hipLaunchKernelGGL(k_curl_blur_bwd, g2, dim3(64, 4), 0, s, eu, ev, h, w, a_bound, ga, g_batch_stride);
+  if (gt_in) {
+    dim3 gc(min(cdiv(h * w, 256), 4096), n);
+    hipLaunchKernelGGL(k_clip_bwd, gc, dim3(256), 0, s, gt_out, t_in, h * w, in_batch_stride, g_batch_stride, t_lo, t_hi, gt_in);
+  }
+  MC_CHECK_LAUNCH();
+  return MC_OK;
+}
+
+int mc_curl_blur_valid_fwd(const float* a, int32_t n, int32_t h, int32_t w, int64_t in_batch_stride, float a_bound, float* u,
+                           float* v, void* stream) {
+  if (!a || !u || !v || n <= 0 || n > 65535 || h <= 0 || w <= 0 || in_batch_stride < (int64_t)(h + 2) * (w + 2)) return MC_EINVAL;
+  dim3 g(cdiv(w, BT_X), cdiv(h, BT_Y), n);
+  hipLaunchKernelGGL(k_curl_blur_fwd<false>, g, dim3(64, 4), 0, (hipStream_t)stream, a, h + 2, w + 2, in_batch_stride, a_bound, u, v);
+  MC_CHECK_LAUNCH();
+  return MC_OK;
+}
+
+int mc_curl_blur_valid_bwd(const float* gu, const float* gv, int32_t n, int32_t h, int32_t w, float a_bound, float* ga,
+                           int64_t g_batch_stride, void* stream) {
+  if (!gu || !gv || !ga || n <= 0 || n > 65535 || h <= 0 || w <= 0 || g_batch_stride < (int64_t)(h + 2) * (w + 2)) return MC_EINVAL;
+  dim3 g(cdiv(w + 2, BT_X), cdiv(h + 2, BT_Y), n);
+  hipLaunchKernelGGL(k_curl_blur_bwd, g, dim3(64, 4), 0, (hipStream_t)stream, gu, gv, h + 2, w + 2, a_bound, ga, g_batch_stride);
   MC_CHECK_LAUNCH();
   return MC_OK;
 }

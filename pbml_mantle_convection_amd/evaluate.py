@@ -393,6 +393,9 @@ def build_arg_parser():
     p.add_argument("-p", "--r_p", type=str, default="zeros")
     p.add_argument("-a", "--act_fn", type=str, default="gelu")
     p.add_argument("-lt", "--loss_type", type=str, default="mass")
+    p.add_argument("-ab", "--a_bound", type=float, default=4.0, help="a_bound of the 'curl' head (the training run's -ab)")
+    p.add_argument("-blurr", "--blurr", type=int, default=0, help="1: the net was trained with -blurr 1 (3 x 3 box mean of the "
+                   "streamfunction inside the 'curl' head)")
     p.add_argument("--data_dir", type=str, default=None, help="directory with sims.pt and <an>/sim_<n>/")
     p.add_argument("--an", type=str, default="cv", help="split whose simulations are scored")
     p.add_argument("--sims", type=int, nargs="*", default=None, help="simulation numbers (default: all of the split)")

@@ -1,6 +1,7 @@
 """Fused training loss on MI355X: Trainer.loss_fn / get_loss arithmetic (reference
 multigpu.py:122-134, 250-305) plus the build-defined Stokes momentum residual, forward AND
-backward in one pass over the fields (libmantle_hip: mc_loss_* / mc_momentum_* / mc_curl_head_* / mc_curl_valid_*).
+backward in one pass over the fields (libmantle_hip: mc_loss_* / mc_momentum_* / mc_curl_head_* / mc_curl_valid_* and, with
+`-blurr 1`, their mc_curl_blur_* twins).
 
 `StokesLoss.evaluate` works on raw device buffers (used by the fused trainer, graph-capturable);
 `StokesLoss.__call__` is the autograd-visible form used by Trainer.get_loss.
@@ -24,7 +25,7 @@ class StokesLoss:
     def __init__(self, p_pred: bool, loss_type: str, loss_scale: bool = False, loss_derivative: bool = False,
                  norm: str = "l1", lambda_mom: float = 0.0, inv_h: float = 126.0, ra: float = 1.0,
                  a_bound: float = 10.0, t_grad: bool = True, has_T: bool = True, curl_valid: bool = False,
-                 advect_cn: Optional[float] = None):
+                 advect_cn: Optional[float] = None, blurr: bool = False):
         if loss_type not in L.LOSS_TYPES:
             raise ValueError(f"loss_type must be one of {list(L.LOSS_TYPES)}")
         if norm not in ("l1", "l2"):
@@ -52,6 +53,12 @@ class StokesLoss:
             raise ValueError("advect_cn is the FluidNet family's temperature term: it needs has_T = False (a Unet predicts T itself)")
         if self.advect_cn is not None and not self.advect_cn > 0.0:
             raise ValueError(f"advect_cn (the ADNet's CN_max) must be > 0, got {advect_cn}")
+        # blurr: the reference's `-blurr 1` for the FluidNet family (DESIGN.md §9 "Blurred streamfunction"): u, v are the curl of
+        # the streamfunction's 3 x 3 box mean; the mean sits inside the head's launches (mc_curl_blur_head_* / mc_curl_blur_valid_*)
+        self.blurr = bool(blurr)
+        if self.blurr and (loss_type != "curl" or self.has_T):
+            raise ValueError("blurr is the streamfunction blur of NewFluidNet / FluidNet: loss_type 'curl' and has_T = False (the "
+                             "Unet's blurr, a randomly drawn Gaussian, is not built)")
         self._shape = None
 
     # ------------------------------------------------------------------
@@ -188,15 +195,16 @@ class StokesLoss:
             # FluidNet: channel 0 = streamfunction on (H+2) x (W+2)
             if Cc > 1:
                 self.gy.zero_()
-            L.call("mc_curl_valid_fwd", yb, N, H, W, Cc * (H + 2) * (W + 2), self.a_bound, L.ptr(self.cu), L.ptr(self.cv), st)
+            L.call("mc_curl_blur_valid_fwd" if self.blurr else "mc_curl_valid_fwd", yb, N, H, W, Cc * (H + 2) * (W + 2), self.a_bound,
+                   L.ptr(self.cu), L.ptr(self.cv), st)
             u, v, T, pbs = self.cu.data_ptr(), self.cv.data_ptr(), None, HW
             gu, gv, gT = self.gcu.data_ptr(), self.gcv.data_ptr(), None
             p = gp = None
         elif self.loss_type == "curl" and not self.has_T:
             # NewFluidNet: channel 0 = streamfunction, 1 = p  (reference pytorch_networks_convae.py:1360-1369)
             self.gy.zero_()
-            L.call("mc_curl_head_fwd", yb, None, N, H, W, Cc * HW, self.a_bound, 0.0, 0.0, L.ptr(self.cu), L.ptr(self.cv),
-                   None, st)
+            L.call("mc_curl_blur_head_fwd" if self.blurr else "mc_curl_head_fwd", yb, None, N, H, W, Cc * HW, self.a_bound, 0.0, 0.0,
+                   L.ptr(self.cu), L.ptr(self.cv), None, st)
             u, v, T, pbs = self.cu.data_ptr(), self.cv.data_ptr(), None, HW
             gu, gv, gT = self.gcu.data_ptr(), self.gcv.data_ptr(), None
             p = yb + 4 * 1 * HW if self.p_pred else None
@@ -247,10 +255,11 @@ class StokesLoss:
             L.call("mc_momentum_adjoint", C.byref(d), T, pbs, ppbs, L.ptr(self.eta), L.ptr(paras), L.ptr(scaler),
                    L.ptr(self.sx), L.ptr(self.sy), gu, gv, gp, gT, st)
         if self.curl_valid:
-            L.call("mc_curl_valid_bwd", gu, gv, N, H, W, self.a_bound, gb, Cc * (H + 2) * (W + 2), st)
+            L.call("mc_curl_blur_valid_bwd" if self.blurr else "mc_curl_valid_bwd", gu, gv, N, H, W, self.a_bound, gb,
+                   Cc * (H + 2) * (W + 2), st)
         elif self.loss_type == "curl" and not self.has_T:
-            L.call("mc_curl_head_bwd", gu, gv, None, None, N, H, W, self.a_bound, 0.0, 0.0, gb, None, Cc * HW, Cc * HW,
-                   L.ptr(self.curl_ws), st)
+            L.call("mc_curl_blur_head_bwd" if self.blurr else "mc_curl_head_bwd", gu, gv, None, None, N, H, W, self.a_bound, 0.0, 0.0,
+                   gb, None, Cc * HW, Cc * HW, L.ptr(self.curl_ws), st)
         elif self.loss_type == "curl":
             L.call("mc_curl_head_bwd", gu, gv, gT, yb + 4 * HW, N, H, W, self.a_bound, 0.0, 1.5, gb, gb + 4 * HW,
                    Cc * HW, Cc * HW, L.ptr(self.curl_ws), st)

@@ -238,11 +238,14 @@ class Trainer:
         if hasattr(self.model_uvp, "set_dropout_seed"):
             self.model_uvp.set_dropout_seed(self.drop_seed)
         a_bound = getattr(self.model_uvp, "a_bound", 10.0)
+        # the reference's `-blurr 1`: NewFluidNet / FluidNet carry the 3 x 3 box filter, which their 'curl' branch alone reads
+        # (DESIGN.md §9 "Blurred streamfunction"); the loss's head launches follow the module
+        self.blurr = bool(fluid and loss_type == "curl" and getattr(self.model_uvp, "blurrer", None) is not None)
         self.loss = StokesLoss(p_pred if network != "convae" else False,
                                loss_type if network != "convae" else "mae", loss_scale, loss_derivative, norm=norm,
                                lambda_mom=lambda_mom, a_bound=a_bound, has_T=not fluid,
                                curl_valid=isinstance(self.model_uvp, FluidNet),   # (u, v on H x W from an (H+2) x (W+2) output)
-                               advect_cn=self.advect_cn)
+                               advect_cn=self.advect_cn, blurr=self.blurr)
         if network == "convae" or fluid:
             self.chan_scale = None                    # these nets see gVTp as it is (reference :139)
         else:
@@ -700,7 +703,8 @@ class Trainer:
         return dict(                                                   # (the .cpu() copies are the device sync)
             header=dict(version=STATE_VERSION, epoch=int(self.epoch_done), world=int(self.world),
                         precision=str(self.model_uvp.precision), network=str(self.net), numel=int(self.flat.numel),
-                        advect=self.advect_cn is not None, CN_max=0.0 if self.advect_cn is None else float(self.advect_cn)),
+                        advect=self.advect_cn is not None, CN_max=0.0 if self.advect_cn is None else float(self.advect_cn),
+                        blurr=bool(self.blurr)),
             layout=self._layout(),
             optimizer=dict(param=self.flat.param.detach().cpu(), exp_avg=self.exp_avg.cpu(), exp_avg_sq=self.exp_avg_sq.cpu(),
                            step_count=self.step_count.cpu(), lr=float(g["lr"]), betas=[b1, b2], eps=eps, weight_decay=wd,
@@ -721,6 +725,10 @@ class Trainer:
         now = (self.advect_cn is not None, 0.0 if self.advect_cn is None else float(self.advect_cn))
         if had != now:
             raise ValueError(f"run state was written with (advect, CN_max) = {had}, this run has {now}: it cannot continue exactly")
+        # so is the streamfunction blur (a state written before it existed has no key: off)
+        if bool(h.get("blurr", False)) != bool(self.blurr):
+            raise ValueError(f"run state was written with blurr = {bool(h.get('blurr', False))}, this run has {bool(self.blurr)}: it "
+                             "cannot continue exactly")
         a, b = state["layout"], self._layout()
         for i, (n0, s0, o0) in enumerate(zip(a["names"], a["shapes"], a["offsets"])):
             if i >= len(b["names"]):

@@ -136,7 +136,8 @@ def pad_uvp(u, v, p=None):
 # --------------------------------------------------------------------------------------------------
 # FluidLayer (reference :702-799): conv -> GroupNorm -> activation -> dropout(p)
 # --------------------------------------------------------------------------------------------------
-def _check_common(act_fn, r_p, dilation, drop_rate=0.0, spectral_conv=False, blurr=False, spectral_ok=False, drop_ok=False):
+def _check_common(act_fn, r_p, dilation, drop_rate=0.0, spectral_conv=False, blurr=False, spectral_ok=False, drop_ok=False,
+                  blurr_ok=False, blurr_why="the streamfunction blur is built for NewFluidNet and FluidNet only"):
     if act_fn not in _SUPPORTED_ACTS:
         raise NotImplementedError(f"act_fn={act_fn!r}: supported on the HIP path: {_SUPPORTED_ACTS} "
                                   "('sine' is undefined in the reference itself)")
@@ -152,8 +153,15 @@ def _check_common(act_fn, r_p, dilation, drop_rate=0.0, spectral_conv=False, blu
                                   "pooled layers; reference default 0)")
     if spectral_conv and not spectral_ok:
         raise NotImplementedError("spectral_conv is built for NewFluidNet and FluidNet (the Unet's spectral layers are not)")
-    if blurr:
-        raise NotImplementedError("blurr is out of scope")
+    if blurr and not blurr_ok:
+        raise NotImplementedError(f"blurr is not built here: {blurr_why}")
+
+
+def _blurrer(blurr):
+    """The reference's box filter (:1163-1172, :1487-1496, there widened to f64): a plain [1, 1, 3, 3] tensor of the f32 value
+    1/9 -- no parameter, no buffer, so the state_dict is the same with and without it.  The HIP heads carry the weight themselves (csrc/curl_head.hip); the tensor
+    is the flag that `Trainer`, `StokesLoss` and the rollout read (`blurrer is not None`)."""
+    return torch.Tensor([[1 / 9, 1 / 9, 1 / 9]] * 3).unsqueeze(0).unsqueeze(0) if blurr else None
 
 
 class FluidLayer(nn.Module, HipNetMixin):
@@ -272,7 +280,10 @@ class Unet(nn.Module, HipNetMixin):
                  r_p="replicate", loss_type="curl", use_symm=False, dilation=1, a_bound=10.0, use_cosine=False,
                  repeats=2, use_skip=False, f=5, p_pred=False, spectral_conv=False, blurr=False, drop_rate=0.0):
         super().__init__()
-        _check_common(act_fn, r_p, dilation, drop_rate, spectral_conv, blurr)
+        _check_common(act_fn, r_p, dilation, drop_rate, spectral_conv, blurr,
+                      blurr_why="the Unet's blurr is a torchvision GaussianBlur((5, 9), sigma=(0.1, 5.0)) whose sigma is drawn at "
+                                "random on every call (reference :1800-1801); only the deterministic 3 x 3 box mean of NewFluidNet "
+                                "and FluidNet is built")
         self.levels, self.loss_type, self.a_bound = levels, loss_type, a_bound
         self.use_cosine, self.repeats, self.use_skip, self.p_pred = use_cosine, repeats, use_skip, p_pred
         self.blurrer = None
@@ -336,17 +347,18 @@ class Unet(nn.Module, HipNetMixin):
 # NewFluidNet (reference :1068-1390) — SURVEY.md §8(f) row N1
 # --------------------------------------------------------------------------------------------------
 class _CurlUV(torch.autograd.Function):
-    """u, v from the streamfunction channel with antisymmetric walls and zero corners (:1360-1388); no T channel."""
+    """u, v from the streamfunction channel with antisymmetric walls and zero corners (:1360-1388); no T channel.  blurr: the
+    streamfunction's 3 x 3 box mean first (:1357-1361), inside the same launches (mc_curl_blur_head_*)."""
 
     @staticmethod
-    def forward(ctx, y, a_bound):
+    def forward(ctx, y, a_bound, blurr=False):
         N, Cc, H, W = y.shape
         y = y.contiguous()
         u = torch.empty((N, H, W), dtype=torch.float32, device=y.device)
         v = torch.empty_like(u)
-        L.call("mc_curl_head_fwd", L.ptr(y), None, N, H, W, Cc * H * W, float(a_bound), 0.0, 0.0, L.ptr(u), L.ptr(v), None,
-               L.stream())
-        ctx.shape, ctx.a_bound = (N, Cc, H, W), float(a_bound)
+        L.call("mc_curl_blur_head_fwd" if blurr else "mc_curl_head_fwd", L.ptr(y), None, N, H, W, Cc * H * W, float(a_bound), 0.0,
+               0.0, L.ptr(u), L.ptr(v), None, L.stream())
+        ctx.shape, ctx.a_bound, ctx.blurr = (N, Cc, H, W), float(a_bound), bool(blurr)
         return u, v
 
     @staticmethod
@@ -357,9 +369,9 @@ class _CurlUV(torch.autograd.Function):
         ws = torch.empty(2 * N * (H - 2) * (W - 2), dtype=torch.float32, device=dev)
         gu = (gu if gu is not None else torch.zeros((N, H, W), device=dev)).contiguous().float()
         gv = (gv if gv is not None else torch.zeros((N, H, W), device=dev)).contiguous().float()
-        L.call("mc_curl_head_bwd", L.ptr(gu), L.ptr(gv), None, None, N, H, W, ctx.a_bound, 0.0, 0.0, L.ptr(gy), None,
-               Cc * H * W, Cc * H * W, L.ptr(ws), L.stream())
-        return gy, None
+        L.call("mc_curl_blur_head_bwd" if ctx.blurr else "mc_curl_head_bwd", L.ptr(gu), L.ptr(gv), None, None, N, H, W, ctx.a_bound,
+               0.0, 0.0, L.ptr(gy), None, Cc * H * W, Cc * H * W, L.ptr(ws), L.stream())
+        return gy, None, None
 
 
 class NewFluidNet(nn.Module, HipNetMixin):
@@ -372,11 +384,12 @@ class NewFluidNet(nn.Module, HipNetMixin):
                  loss_type="mae", use_symm=False, dilation=1, a_bound=4.0, use_cosine=False, repeats=3, use_skip=False,
                  f=3, p_pred=True, spectral_conv=False, blurr=False, drop_rate=0.0, factor=2):
         super().__init__()
-        _check_common(act_fn, r_p, dilation, drop_rate, spectral_conv, blurr, spectral_ok=True, drop_ok=True)
+        _check_common(act_fn, r_p, dilation, drop_rate, spectral_conv, blurr, spectral_ok=True, drop_ok=True, blurr_ok=True)
         self.levels, self.loss_type, self.a_bound = levels, loss_type, a_bound
         self.use_cosine, self.repeats, self.use_skip, self.p_pred = use_cosine, repeats, use_skip, p_pred
         self.c_h, self.c_i, self.c_o = c_h, c_i, c_o
-        self.blurrer = None
+        # (reference :1163-1172; read in the 'curl' branch only: with 'mae' / 'mass' the flag is accepted and ignored, as there)
+        self.blurrer = _blurrer(blurr)
         self.r_p = "constant" if r_p == "zeros" else r_p
         graph = newfluidnet_graph(levels, c_i, c_h, c_o, act=act_fn, r_p=r_p, use_symm=use_symm, repeats=repeats, f=f,
                                   factor=factor, spectral=spectral_conv, drop_rate=drop_rate)
@@ -421,8 +434,8 @@ class NewFluidNet(nn.Module, HipNetMixin):
             # (the reference returns p un-squeezed, [B,1,H,W], :1351-1358)
             return y[:, 0], y[:, 1], (y[:, 2:3] if self.p_pred else None)
         elif self.loss_type == "curl":
-            u, v = _CurlUV.apply(y, self.a_bound)
-            return u, v, (y[:, 1] if self.p_pred else None)
+            u, v = _CurlUV.apply(y, self.a_bound, self.blurrer is not None)
+            return u, v, (y[:, 1] if self.p_pred else None)               # (p stays the unblurred channel)
         raise ValueError(self.loss_type)
 
 
@@ -431,17 +444,19 @@ class NewFluidNet(nn.Module, HipNetMixin):
 # --------------------------------------------------------------------------------------------------
 class _CurlValid(torch.autograd.Function):
     """u, v on H x W from the streamfunction channel of an (H+2) x (W+2) output (:1681-1697): plain centred differences,
-    no wall fix-up (mc_curl_valid_fwd / mc_curl_valid_bwd)."""
+    no wall fix-up (mc_curl_valid_fwd / mc_curl_valid_bwd).  blurr: of the 3 x 3 box mean of the grown streamfunction
+    (:1682-1686; mc_curl_blur_valid_fwd / mc_curl_blur_valid_bwd)."""
 
     @staticmethod
-    def forward(ctx, y, a_bound):
+    def forward(ctx, y, a_bound, blurr=False):
         N, Cc, Hy, Wy = y.shape
         H, W = Hy - 2, Wy - 2
         y = y.contiguous()
         u = torch.empty((N, H, W), dtype=torch.float32, device=y.device)
         v = torch.empty_like(u)
-        L.call("mc_curl_valid_fwd", L.ptr(y), N, H, W, Cc * Hy * Wy, float(a_bound), L.ptr(u), L.ptr(v), L.stream())
-        ctx.shape, ctx.a_bound = (N, Cc, Hy, Wy), float(a_bound)
+        L.call("mc_curl_blur_valid_fwd" if blurr else "mc_curl_valid_fwd", L.ptr(y), N, H, W, Cc * Hy * Wy, float(a_bound), L.ptr(u),
+               L.ptr(v), L.stream())
+        ctx.shape, ctx.a_bound, ctx.blurr = (N, Cc, Hy, Wy), float(a_bound), bool(blurr)
         return u, v
 
     @staticmethod
@@ -452,8 +467,9 @@ class _CurlValid(torch.autograd.Function):
         gy = (torch.zeros if Cc > 1 else torch.empty)((N, Cc, Hy, Wy), dtype=torch.float32, device=dev)
         gu = (gu if gu is not None else torch.zeros((N, Hy - 2, Wy - 2), device=dev)).contiguous().float()
         gv = (gv if gv is not None else torch.zeros((N, Hy - 2, Wy - 2), device=dev)).contiguous().float()
-        L.call("mc_curl_valid_bwd", L.ptr(gu), L.ptr(gv), N, Hy - 2, Wy - 2, ctx.a_bound, L.ptr(gy), Cc * Hy * Wy, L.stream())
-        return gy, None
+        L.call("mc_curl_blur_valid_bwd" if ctx.blurr else "mc_curl_valid_bwd", L.ptr(gu), L.ptr(gv), N, Hy - 2, Wy - 2, ctx.a_bound,
+               L.ptr(gy), Cc * Hy * Wy, L.stream())
+        return gy, None, None
 
 
 class FluidNet(nn.Module, HipNetMixin):
@@ -469,7 +485,7 @@ class FluidNet(nn.Module, HipNetMixin):
                  loss_type="mae", use_symm=False, dilation=1, a_bound=4.0, use_cosine=False, repeats=3, use_skip=False,
                  f=3, p_pred=True, spectral_conv=False, blurr=False, drop_rate=0.0, factor=2):
         super().__init__()
-        _check_common(act_fn, r_p, dilation, drop_rate, spectral_conv, blurr, spectral_ok=True, drop_ok=True)
+        _check_common(act_fn, r_p, dilation, drop_rate, spectral_conv, blurr, spectral_ok=True, drop_ok=True, blurr_ok=True)
         if loss_type in ("mae", "mass"):
             raise NotImplementedError(f"FluidNet with loss_type={loss_type!r} fails in the reference (its forward skips conv.1, so "
                                       "GroupNorm sees c_h * levels + c_i channels); only 'curl' is built")
@@ -486,7 +502,7 @@ class FluidNet(nn.Module, HipNetMixin):
         self.levels, self.loss_type, self.a_bound = levels, loss_type, a_bound
         self.use_cosine, self.repeats, self.use_skip, self.p_pred = use_cosine, repeats, use_skip, p_pred
         self.c_h, self.c_i, self.c_o = c_h, c_i, c_o
-        self.blurrer = None
+        self.blurrer = _blurrer(blurr)                                  # (reference :1487-1496)
         self.r_p = "constant" if r_p == "zeros" else r_p
         self.act = {"selu": nn.SELU, "tanh": nn.Tanh, "elu": nn.ELU, "silu": nn.SiLU, "relu": nn.ReLU, "gelu": nn.GELU}[act_fn]()
         graph = fluidnet_graph(levels, c_i, c_h, c_o, act=act_fn, r_p=r_p, use_symm=use_symm, repeats=repeats, f=f,
@@ -523,7 +539,7 @@ class FluidNet(nn.Module, HipNetMixin):
         return self._run_graph(inputs)
 
     def forward(self, inputs):
-        u, v = _CurlValid.apply(self.features(inputs), self.a_bound)
+        u, v = _CurlValid.apply(self.features(inputs), self.a_bound, self.blurrer is not None)
         return u, v, None
 
 

@@ -461,6 +461,9 @@ def build_arg_parser():
     p.add_argument("-p", "--r_p", type=str, default="zeros")
     p.add_argument("-a", "--act_fn", type=str, default="gelu")
     p.add_argument("-lt", "--loss_type", type=str, default="mass")
+    p.add_argument("-ab", "--a_bound", type=float, default=4.0, help="a_bound of the 'curl' head (the training run's -ab)")
+    p.add_argument("-blurr", "--blurr", type=int, default=0, help="1: the net was trained with -blurr 1 (3 x 3 box mean of the "
+                   "streamfunction inside the 'curl' head)")
     p.add_argument("--params", type=str, required=True, help="CSV: one row raq,fkt,fkp per member")
     p.add_argument("--steps", type=int, required=True)
     p.add_argument("--t_end", type=float, default=None)
@@ -485,11 +488,15 @@ def build_arg_parser():
 
 
 def build_stokes(a, dev):
-    """The NewFluidNet of the command line (7 input channels, u / v / p outputs), weights from --weights or seeded."""
+    """The NewFluidNet of the command line (7 input channels, u / v / p outputs), weights from --weights or seeded.  The output
+    channels are the training command line's (`multigpu.channels_for`: 3, or 2 with `-lt curl`, whose streamfunction stands for
+    u and v), so that a checkpoint of `-lt curl [-blurr 1] -pp 1` loads; `-ab` is that run's a_bound."""
+    from .multigpu import channels_for
     from .pytorch_networks_convae import NewFluidNet
     torch.manual_seed(a.seed)
-    m = NewFluidNet(a.levels, 7, a.c_h, 3, dev, a.act_fn, a.r_p, a.loss_type, use_symm=True, repeats=a.repeats, f=a.kernel,
-                    p_pred=True)
+    m = NewFluidNet(a.levels, 7, a.c_h, channels_for("newfluidnet", a.loss_type, True)[1], dev, a.act_fn, a.r_p, a.loss_type,
+                    use_symm=True, a_bound=getattr(a, "a_bound", 4.0), repeats=a.repeats, f=a.kernel, p_pred=True,
+                    blurr=getattr(a, "blurr", 0) == 1)
     if a.weights:
         m.load_state_dict(torch.load(a.weights, map_location="cpu"))
     return m.to(dev)

@@ -977,10 +977,67 @@ def g24():
         **{("sd2/" + k): v for k, v in m.state_dict().items()})
 
 
+# ------------------------------------------------------------------ G25 blurred streamfunction (-blurr 1)
+def _edges(o):
+    """The complete two outermost rows and columns of a [B, H, W] field: where the blur's replicate rule meets the wall
+    fix-up, which a strided sample can miss."""
+    return dict(top=o[:, :2], bottom=o[:, -2:], left=o[:, :, :2], right=o[:, :, -2:])
+
+
+def _g25_one(name, m, head_conv, x, cts, extra):
+    """One network with blurr=True: y0 (the streamfunction channel the head reads, complete and in f64, so that the head's
+    reference can be checked on the CPU without running the trunk), samples and the complete edges of u, v, p, dx, the last
+    conv's gradients in full and samples of the others."""
+    kept = {}
+    hook = head_conv.register_forward_hook(lambda mod, inp, out: kept.update(y=out.detach()))
+    outs = m(x)
+    hook.remove()
+    y = kept["y"] - kept["y"].mean(dim=(2, 3), keepdim=True)
+    save, loss = {"y0": y[:, 0]}, 0.0
+    for n, o, ct in zip("uvp", outs, cts):
+        if o is None:
+            continue
+        loss = loss + (o * ct.view(o.shape)).sum()
+        save["out/" + n] = fields.strided_sample(o.detach().numpy(), 5003)
+        if n in "uv":
+            save.update({f"edge/{n}/{k}": e.detach() for k, e in _edges(o).items()})
+    loss.backward()
+    last = [k for k, _ in m.named_parameters() if k.startswith("conv.3.")]
+    grads = {"grad/" + k.replace("conv.1.c.", "conv.1."): (p.grad if k in last else fields.strided_sample(p.grad.numpy(), 257))
+             for k, p in m.named_parameters()}
+    npz(name, dx_sample=fields.strided_sample(x.grad.numpy(), 1021), **save, **grads, **extra)
+
+
+def g25():
+    B, H, W = 1, 128, 506
+    # (a) g12's curl_rep NewFluidNet (same constructor arguments and seed, so the weights are g12_newfluidnet_curl_rep's sd/*
+    # and the cotangents its ct/*) with blurr=True
+    m = P.NewFluidNet(3, 7, 8, 3, CPU, "selu", "replicate", "curl", use_symm=False, repeats=2, f=5, p_pred=True, blurr=True).double()
+    randomize_(m, 120)
+    assert m.blurrer is not None and m.blurrer.dtype == f64 and "blurrer" not in m.state_dict()
+    x = torch.from_numpy(fields.unet_input(B, H, W, 121, c_i=7)).requires_grad_(True)
+    cts = [rnd((B, H, W), 122 + 2 * i) for i in range(3)]                 # (g12's seeds: 122 + the entries saved so far)
+    _g25_one("g25_newfluidnet_blurr", m, m.conv[3], x, cts,
+             dict(cfg=np.array([3, 7, 8, 3, 2, 5, 1, 0]), a_bound=np.array(float(m.a_bound)), weights=np.array("g12_newfluidnet_curl_rep")))
+    # (b) g22's learned FluidNet (weights: g22_fluidnet_learned's sd/*; cotangents generated as g22 does) with blurr=True
+    seed = 220
+    m = P.FluidNet(2, 7, 8, 1, CPU, "gelu", "learned", "curl", use_symm=True, a_bound=10, repeats=1, f=5, p_pred=False, blurr=True).double()
+    randomize_(m, seed)
+    with torch.no_grad():
+        g_ = torch.Generator().manual_seed(seed + 1)
+        for n, p in m.named_parameters():
+            if n.endswith("learnable_bias"):
+                p.copy_((0.1 * torch.randn(p.shape, generator=g_)).float().double())
+    x = torch.from_numpy(fields.unet_input(B, H, W, seed + 2, c_i=7)).requires_grad_(True)
+    cts = [torch.from_numpy(fields.smooth_field(B, H, W, seed + 3 + i).astype(np.float32)).to(f64) for i in range(2)]
+    _g25_one("g25_fluidnet_blurr", m, m.conv[3], x, cts,
+             dict(cfg=np.array([2, 7, 8, 1, 1, 5, 0, 1]), a_bound=np.array(10.0), weights=np.array("g22_fluidnet_learned")))
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     torch.set_num_threads(8)
     only = sys.argv[1:]
-    for fn in (g1, g2, g3, g4, g5, g6, g7, g8, g9, g10, g11, g12, g13, g14, g15, g16, g17, g18, g19, g20, g21, g22, g23, g24):
+    for fn in (g1, g2, g3, g4, g5, g6, g7, g8, g9, g10, g11, g12, g13, g14, g15, g16, g17, g18, g19, g20, g21, g22, g23, g24, g25):
         if not only or fn.__name__ in only:
             fn()
