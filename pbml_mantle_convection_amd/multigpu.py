@@ -28,6 +28,7 @@ from torch.utils.data import DataLoader, Dataset
 
 from . import _lib as L
 from .datasetio import *  # noqa: F401,F403  (reference does the same star import)
+from .heads import CurlHead, HeadForm
 from .hipnet import FlatParams
 from .losses import StokesLoss
 from .pytorch_networks_convae import ADNet, ConvAE, FluidNet, NewFluidNet, Unet, count_parameters
@@ -313,13 +314,14 @@ class Trainer:
         x.copy_(gVTp)
         p3 = paras.to(torch.float32).reshape(N, 3).contiguous()
         m = self.model_uvp
+        # Unet.forward's head (u, v from the streamfunction; T clipped)
+        head = CurlHead(HeadForm.WALL_T, False, float(m.a_bound)) if m.loss_type == "curl" else None
         for i in range(R * R - 1):
             y = fwd(x)
             Cc = y.shape[1]
-            if m.loss_type == "curl":                            # Unet.forward's head (u, v from the streamfunction; T clipped)
+            if head is not None:
                 u, v, T = self._roll_uvT[0], self._roll_uvT[1], self._roll_uvT[2]
-                L.call("mc_curl_head_fwd", L.ptr(y), y.data_ptr() + 4 * H * W, N, H, W, Cc * H * W, float(m.a_bound), 0.0, 1.5,
-                       L.ptr(u), L.ptr(v), L.ptr(T), L.stream())
+                head.forward(L.ptr(y), Cc * H * W, N, H, W, L.ptr(u), L.ptr(v), L.ptr(T), L.stream())
                 pu, pv, pT, stride = L.ptr(u), L.ptr(v), L.ptr(T), H * W
             else:
                 pu, pv, pT, stride = y.data_ptr(), y.data_ptr() + 4 * H * W, y.data_ptr() + 8 * H * W, Cc * H * W
@@ -336,9 +338,7 @@ class Trainer:
             with torch.no_grad():
                 gVTp = self._roll_chain(gVTp.contiguous(), None if paras is None else paras.to(self.device), self._features)
         y = self._features(gVTp)
-        sc = None
-        if self.loss.lambda_mom != 0.0 or self.advect_cn is not None:
-            sc = scaler.to(self.device, torch.float32) if scaler is not None else None
+        sc = scaler.to(self.device, torch.float32) if ("scaler" in self.loss.needs and scaler is not None) else None
         out8 = self.loss(y, uvp, yc.to(self.device) if yc is not None else None,
                          paras.to(self.device) if paras is not None else None, sc, self._advect_args(gVTp, sc))
         return out8[0], out8[1].detach(), out8[2].detach(), out8[3].detach(), out8[4].detach(), out8[5].detach()
@@ -387,7 +387,7 @@ class Trainer:
 
     def _advect_args(self, gVTp, scaler):
         """(x, scaler) of the advection loss, None without model_AD: the batch's own input carries the grid and the temperature."""
-        if self.advect_cn is None:
+        if "advect" not in self.loss.needs:
             return None
         if scaler is None:
             raise ValueError("the advection loss (model_AD) needs the batch's velocity scaler [N]")
@@ -400,7 +400,7 @@ class Trainer:
         next batch the same one) -- in a captured step BEFORE the batch is copied into the static buffer, never inside a
         capture.  A loader that fills `input_buffers()` in place passes the static buffer itself: no copy, no check, and the
         loader is responsible for its batches (`validate_mesh`)."""
-        if yc is None or self.loss.lambda_mom == 0.0 or yc.dim() < 3 or yc.shape[0] <= 1:
+        if yc is None or "yc" not in self.loss.needs or yc.dim() < 3 or yc.shape[0] <= 1:
             return
         if torch.cuda.is_current_stream_capturing():
             return
@@ -530,11 +530,8 @@ class Trainer:
         evaluation batch of another size runs on an engine / loss pair of its own (same parameters)."""
         if self._graph is not None and tuple(gVTp.shape) != tuple(self._static["gVTp"].shape):
             if getattr(self, "_eval_pair", None) is None:
-                import copy
                 from .engine import Engine
-                lo = copy.copy(self.loss)
-                lo._shape, lo._frozen = None, False
-                self._eval_pair = (Engine(self.model_uvp._graph, self.model_uvp.precision), lo)
+                self._eval_pair = (Engine(self.model_uvp._graph, self.model_uvp.precision), self.loss.unplanned_copy())
                 self.model_uvp.seed_engine(self._eval_pair[0])      # (it never draws a mask: evaluation runs without dropout)
             return self._fwd_bwd(gVTp, uvp, yc, paras, scaler, train=False, eng=self._eval_pair[0], loss=self._eval_pair[1])
         return self._fwd_bwd(gVTp, uvp, yc, paras, scaler, train=False)
@@ -543,10 +540,10 @@ class Trainer:
     def _prep(self, gVTp, uvp, scaler, paras, yc):
         gVTp = gVTp.to(self.device, torch.float32, non_blocking=True).contiguous()
         uvp = uvp.to(self.device, torch.float32, non_blocking=True).contiguous()
-        need = self.loss.lambda_mom != 0.0
-        yc = yc.to(self.device, torch.float32) if (need and yc is not None) else None
-        paras = paras.to(self.device, torch.float32) if ((need or self._rolls()) and paras is not None) else None
-        scaler = scaler.to(self.device, torch.float32) if ((need or self.advect_cn is not None) and scaler is not None) else None
+        needs = self.loss.needs
+        yc = yc.to(self.device, torch.float32) if ("yc" in needs and yc is not None) else None
+        paras = paras.to(self.device, torch.float32) if (("paras" in needs or self._rolls()) and paras is not None) else None
+        scaler = scaler.to(self.device, torch.float32) if ("scaler" in needs and scaler is not None) else None
         return gVTp, uvp, yc, paras, scaler
 
     def _run_batch(self, gVTp, uvp, scaler, is_train, paras=None, yc=None, sync=True):

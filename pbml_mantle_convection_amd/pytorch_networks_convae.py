@@ -18,6 +18,7 @@ import torch.optim as optim
 
 from . import _lib as L
 from .engine import convae_graph, fluid_groups, fluid_sym_h, fluidnet_graph, newfluidnet_graph, single_layer_graph, unet_graph
+from .heads import CurlHead, HeadForm
 from .hipnet import HipNetMixin
 from .learned_padding import BoundaryLearnedConvolution2D   # noqa: F401  (reference :802-1065)
 from .symmetric_layers_torch import SymmetricConv2d
@@ -240,33 +241,43 @@ class SpectralFluidLayer(nn.Module, HipNetMixin):
 # --------------------------------------------------------------------------------------------------
 # curl head (Unet :2038-2070) as an autograd function over the HIP kernels
 # --------------------------------------------------------------------------------------------------
+def _head_forward(ctx, head, y, n_out):
+    """The head's n_out planes [N, H, W] of the f32 network output y [N, C, Hy, Wy] (and y as the launch read it)."""
+    N, Cc, Hy, Wy = y.shape
+    H, W = head.out_hw(Hy, Wy)
+    y = y.contiguous()
+    outs = tuple(torch.empty((N, H, W), dtype=torch.float32, device=y.device) for _ in range(n_out))
+    head.forward(L.ptr(y), Cc * Hy * Wy, N, H, W, *(L.ptr(o) for o in outs), stream=L.stream())
+    ctx.head, ctx.shape = head, (N, Cc, Hy, Wy)
+    return y, outs
+
+
+def _head_backward(ctx, grads, y=None):
+    """d/dy from the gradients of the head's planes (gu, gv[, gT]); y: the saved output, which the T clip reads."""
+    head, (N, Cc, Hy, Wy) = ctx.head, ctx.shape
+    H, W = head.out_hw(Hy, Wy)
+    dev = next(g.device for g in grads if g is not None)
+    # the valid head writes every pixel of channel 0: only further channels need zeros; the wall heads add into zeros
+    zeros = torch.zeros if (head.form is not HeadForm.VALID or Cc > 1) else torch.empty
+    gy = zeros((N, Cc, Hy, Wy), dtype=torch.float32, device=dev)
+    ws = torch.empty(head.ws_floats(N, H, W), dtype=torch.float32, device=dev) if head.ws_floats(N, H, W) else None
+    g = [(g if g is not None else torch.zeros((N, H, W), device=dev)).contiguous().float() for g in grads]
+    head.backward(L.ptr(g[0]), L.ptr(g[1]), L.ptr(g[2]) if len(g) > 2 else None, L.ptr(y), Cc * Hy * Wy, N, H, W, L.ptr(gy),
+                  Cc * Hy * Wy, L.ptr(ws), L.stream())
+    return gy
+
+
 class _CurlHead(torch.autograd.Function):
     @staticmethod
     def forward(ctx, y, a_bound):
         """y: [N, C, H, W] f32 network output; channel 0 = streamfunction, channel 1 = T."""
-        N, Cc, H, W = y.shape
-        y = y.contiguous()
-        u = torch.empty((N, H, W), dtype=torch.float32, device=y.device)
-        v = torch.empty_like(u)
-        Tc = torch.empty_like(u)
-        L.call("mc_curl_head_fwd", L.ptr(y), y.data_ptr() + 4 * H * W, N, H, W, Cc * H * W, float(a_bound), 0.0, 1.5,
-               L.ptr(u), L.ptr(v), L.ptr(Tc), L.stream())
+        y, outs = _head_forward(ctx, CurlHead(HeadForm.WALL_T, False, float(a_bound)), y, 3)
         ctx.save_for_backward(y)
-        ctx.a_bound = float(a_bound)
-        return u, v, Tc
+        return outs
 
     @staticmethod
     def backward(ctx, gu, gv, gT):
-        (y,) = ctx.saved_tensors
-        N, Cc, H, W = y.shape
-        gy = torch.zeros_like(y)
-        ws = torch.empty(2 * N * (H - 2) * (W - 2), dtype=torch.float32, device=y.device)
-        gu = (gu if gu is not None else torch.zeros((N, H, W), device=y.device)).contiguous().float()
-        gv = (gv if gv is not None else torch.zeros((N, H, W), device=y.device)).contiguous().float()
-        gT = (gT if gT is not None else torch.zeros((N, H, W), device=y.device)).contiguous().float()
-        L.call("mc_curl_head_bwd", L.ptr(gu), L.ptr(gv), L.ptr(gT), y.data_ptr() + 4 * H * W, N, H, W, ctx.a_bound,
-               0.0, 1.5, L.ptr(gy), gy.data_ptr() + 4 * H * W, Cc * H * W, Cc * H * W, L.ptr(ws), L.stream())
-        return gy, None
+        return _head_backward(ctx, (gu, gv, gT), ctx.saved_tensors[0]), None
 
 
 # --------------------------------------------------------------------------------------------------
@@ -348,30 +359,15 @@ class Unet(nn.Module, HipNetMixin):
 # --------------------------------------------------------------------------------------------------
 class _CurlUV(torch.autograd.Function):
     """u, v from the streamfunction channel with antisymmetric walls and zero corners (:1360-1388); no T channel.  blurr: the
-    streamfunction's 3 x 3 box mean first (:1357-1361), inside the same launches (mc_curl_blur_head_*)."""
+    streamfunction's 3 x 3 box mean first (:1357-1361), inside the same launches."""
 
     @staticmethod
     def forward(ctx, y, a_bound, blurr=False):
-        N, Cc, H, W = y.shape
-        y = y.contiguous()
-        u = torch.empty((N, H, W), dtype=torch.float32, device=y.device)
-        v = torch.empty_like(u)
-        L.call("mc_curl_blur_head_fwd" if blurr else "mc_curl_head_fwd", L.ptr(y), None, N, H, W, Cc * H * W, float(a_bound), 0.0,
-               0.0, L.ptr(u), L.ptr(v), None, L.stream())
-        ctx.shape, ctx.a_bound, ctx.blurr = (N, Cc, H, W), float(a_bound), bool(blurr)
-        return u, v
+        return _head_forward(ctx, CurlHead(HeadForm.WALL, bool(blurr), float(a_bound)), y, 2)[1]
 
     @staticmethod
     def backward(ctx, gu, gv):
-        N, Cc, H, W = ctx.shape
-        dev = gu.device if gu is not None else gv.device
-        gy = torch.zeros((N, Cc, H, W), dtype=torch.float32, device=dev)
-        ws = torch.empty(2 * N * (H - 2) * (W - 2), dtype=torch.float32, device=dev)
-        gu = (gu if gu is not None else torch.zeros((N, H, W), device=dev)).contiguous().float()
-        gv = (gv if gv is not None else torch.zeros((N, H, W), device=dev)).contiguous().float()
-        L.call("mc_curl_blur_head_bwd" if ctx.blurr else "mc_curl_head_bwd", L.ptr(gu), L.ptr(gv), None, None, N, H, W, ctx.a_bound,
-               0.0, 0.0, L.ptr(gy), None, Cc * H * W, Cc * H * W, L.ptr(ws), L.stream())
-        return gy, None, None
+        return _head_backward(ctx, (gu, gv)), None, None
 
 
 class NewFluidNet(nn.Module, HipNetMixin):
@@ -444,32 +440,15 @@ class NewFluidNet(nn.Module, HipNetMixin):
 # --------------------------------------------------------------------------------------------------
 class _CurlValid(torch.autograd.Function):
     """u, v on H x W from the streamfunction channel of an (H+2) x (W+2) output (:1681-1697): plain centred differences,
-    no wall fix-up (mc_curl_valid_fwd / mc_curl_valid_bwd).  blurr: of the 3 x 3 box mean of the grown streamfunction
-    (:1682-1686; mc_curl_blur_valid_fwd / mc_curl_blur_valid_bwd)."""
+    no wall fix-up.  blurr: of the 3 x 3 box mean of the grown streamfunction (:1682-1686)."""
 
     @staticmethod
     def forward(ctx, y, a_bound, blurr=False):
-        N, Cc, Hy, Wy = y.shape
-        H, W = Hy - 2, Wy - 2
-        y = y.contiguous()
-        u = torch.empty((N, H, W), dtype=torch.float32, device=y.device)
-        v = torch.empty_like(u)
-        L.call("mc_curl_blur_valid_fwd" if blurr else "mc_curl_valid_fwd", L.ptr(y), N, H, W, Cc * Hy * Wy, float(a_bound), L.ptr(u),
-               L.ptr(v), L.stream())
-        ctx.shape, ctx.a_bound, ctx.blurr = (N, Cc, Hy, Wy), float(a_bound), bool(blurr)
-        return u, v
+        return _head_forward(ctx, CurlHead(HeadForm.VALID, bool(blurr), float(a_bound)), y, 2)[1]
 
     @staticmethod
     def backward(ctx, gu, gv):
-        N, Cc, Hy, Wy = ctx.shape
-        dev = gu.device if gu is not None else gv.device
-        # the kernel writes every pixel of channel 0; only further channels need zeros
-        gy = (torch.zeros if Cc > 1 else torch.empty)((N, Cc, Hy, Wy), dtype=torch.float32, device=dev)
-        gu = (gu if gu is not None else torch.zeros((N, Hy - 2, Wy - 2), device=dev)).contiguous().float()
-        gv = (gv if gv is not None else torch.zeros((N, Hy - 2, Wy - 2), device=dev)).contiguous().float()
-        L.call("mc_curl_blur_valid_bwd" if ctx.blurr else "mc_curl_valid_bwd", L.ptr(gu), L.ptr(gv), N, Hy - 2, Wy - 2, ctx.a_bound,
-               L.ptr(gy), Cc * Hy * Wy, L.stream())
-        return gy, None, None
+        return _head_backward(ctx, (gu, gv)), None, None
 
 
 class FluidNet(nn.Module, HipNetMixin):
